@@ -9,12 +9,16 @@ all-gathered over RCCL and each rank writes its row block of K (strong scaling:
 one K per step for the whole job).  On one GPU the steps are pipelined over two HIP
 streams: step s+1's front (Laplacian, walks, Phi, transpose) starts when step s's Gram
 tiles finish and runs beside step s's HBM-bound mirror pass; every step still runs its
-whole path, and `serial_ms_per_step` reports the un-pipelined latency beside `value`.
+whole path.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with a
-`roofline` object for the dominant kernel (gram_sparse) and a `cpu_baseline`
-object (the C oracle -- a restatement of the reference's CPU algorithm -- on the
-host cores, bounded sample, extrapolated; rank 0 at N = 1 only).
+A plain run sets up, warms up, times --steps steps, writes the last timed step's outputs if
+--dump-outputs DIR is given, and prints ONE JSON line on rank 0 (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...) with a `roofline` object for the dominant kernel
+(gram_sparse) from the HIP events of the timed steps.  --full adds everything that takes runs of its
+own: the in-run K parity check, `serial_ms_per_step` (the un-pipelined latency beside `value`) with the
+walk kernel's roofline, the gather roofline, the dense-path MFMA legs, and a `cpu_baseline` object (the
+C oracle -- a restatement of the reference's CPU algorithm -- on the host cores, bounded sample,
+extrapolated; rank 0 at N = 1 only).
 """
 from __future__ import annotations
 
@@ -103,6 +107,87 @@ def _device_tensors(obj, depth: int = 3):
     for v in (vars(obj).values() if hasattr(obj, "__dict__") else []):
         out += _device_tensors(v, depth - 1)
     return out
+
+
+DUMP_SEED = 20240  # --dump-outputs: the seed of every sampled index set (the same rows / columns in every run)
+DUMP_MATRIX_BYTES = 32 << 20  # ... a dense output's share (whole when it fits, else a rows x columns sample)
+DUMP_PHI_ENTRIES = 1 << 20    # ... Phi's entries kept (8 + 4 bytes each: column as float64, value as float32)
+
+
+def _save_npy(out_dir: str, name: str, arr) -> None:
+    """DIR/<name>.npy, float32 or float64 (integers as float64: exact below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arr = np.ascontiguousarray(arr)
+    if arr.dtype not in (np.float32, np.float64):
+        arr = arr.astype(np.float64)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
+def _sample_indices(n: int, k: int, stream: int) -> np.ndarray:
+    """min(k, n) of range(n), sorted, the same in every run (seeded; `stream` separates rows from columns)."""
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng([DUMP_SEED, stream]).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_matrix(out_dir: str, name: str, M, budget: int = DUMP_MATRIX_BYTES) -> None:
+    """A dense device matrix (its logical block) as <name>.npy when it fits in `budget` bytes; else the
+    sub-matrix of a seeded choice of up to 1024 rows and as many columns as fit, as <name>_sample.npy with
+    <name>_sample_rows.npy / <name>_sample_cols.npy (the chosen indices) beside it."""
+    import torch
+
+    rows, cols = int(M.shape[0]), int(M.shape[1])
+    if rows * cols * M.element_size() <= budget:
+        _save_npy(out_dir, name, M.contiguous().cpu().numpy())
+        return
+    ri = _sample_indices(rows, 1024, 0)
+    ci = _sample_indices(cols, max(1, budget // (M.element_size() * len(ri))), 1)
+    sub = M[torch.from_numpy(ri).to(M.device)][:, torch.from_numpy(ci).to(M.device)]
+    _save_npy(out_dir, name + "_sample", sub.contiguous().cpu().numpy())
+    _save_npy(out_dir, name + "_sample_rows", ri)
+    _save_npy(out_dir, name + "_sample_cols", ci)
+
+
+def dump_phi(out_dir: str, name: str, phi, budget_entries: int = DUMP_PHI_ENTRIES) -> None:
+    """A CSR Phi on the device: every row's entry count (<name>_row_counts.npy), and the entries (columns,
+    values: <name>_sample_cols.npy, <name>_sample_vals.npy) of a seeded choice of rows
+    (<name>_sample_rows.npy), rows kept in order while their entries fit in `budget_entries`."""
+    import torch
+
+    ptr = phi.ptr.cpu().numpy().astype(np.int64)
+    counts = np.diff(ptr)
+    _save_npy(out_dir, name + "_row_counts", counts)
+    ri = _sample_indices(phi.n_rows, 4096, 2)
+    ri = ri[:int(np.searchsorted(np.cumsum(counts[ri]), budget_entries, side="right"))]
+    ent = np.concatenate([np.arange(ptr[r], ptr[r + 1], dtype=np.int64) for r in ri]) if len(ri) else \
+        np.zeros(0, np.int64)
+    sel = torch.from_numpy(ent).to(phi.idx.device)
+    _save_npy(out_dir, name + "_sample_rows", ri)
+    _save_npy(out_dir, name + "_sample_cols", phi.idx[sel].cpu().numpy())
+    _save_npy(out_dir, name + "_sample_vals", phi.val32[sel].cpu().numpy())
+
+
+class RunAhead:
+    """Bounds how many steps the host enqueues ahead of the GPU: ``step()`` after a step's launches records an
+    event on `stream` and waits for the event of the step `depth` steps back (depth 0: no bound).  The queue
+    stays `depth` steps deep, so the GPU never idles, while the buffers every front allocates are freed at the
+    GPU's pace: unbounded, a long run's fronts (0.8 GB of padded Phi rows each at C4, held until their step
+    has run) outgrow HBM, the caching allocator falls back to synchronising frees and reallocations, and runs
+    of 100+ steps measured 23.5-55 ms per step instead of 23.5."""
+
+    def __init__(self, stream, depth: int):
+        self.stream, self.depth, self.events = stream, depth, []
+
+    def step(self):
+        import torch
+
+        if self.depth <= 0:
+            return
+        ev = torch.cuda.Event()
+        ev.record(self.stream)
+        self.events.append(ev)
+        if len(self.events) > self.depth:
+            self.events.pop(0).synchronize()
 
 
 def init_distributed(local_rank: int) -> int:
@@ -276,12 +361,21 @@ def main_predict(args):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
+    samples = None
+    for s_ in range(args.steps):
+        if args.dump_outputs and s_ + 1 == args.steps:
+            samples = step(True)
+        else:
+            step(True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     t = time.perf_counter() - t0
+    if args.dump_outputs and samples is not None:
+        # the last timed step's posterior samples at the test nodes (n_test x n_samples)
+        dump_matrix(args.dump_outputs, "posterior_samples" + (f"_rank{rank}" if world > 1 else ""), samples,
+                    DUMP_MATRIX_BYTES // world)
+    del samples
     if world > 1:
         tt = torch.tensor([t], dtype=torch.float64, device=eng.device)
         dist_all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -319,7 +413,7 @@ def main_predict(args):
                      "gather_note": "X rows gathered per CSR entry (L2/Infinity-Cache served; MI355X_MICROARCH.md "
                                     "'Indexed rows': ~17 TB/s L2-resident, ~8.6 TB/s Infinity Cache)"},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_predict(_phi_host(phi), perm[:n_tr], perm[n_tr:n_tr + n_te],
                                                    y.cpu().numpy().astype(np.float64), noise, S, its[0])
     if rank == 0:
@@ -420,7 +514,9 @@ def main_c3(args):
             done.record(side)
         return dense, done
 
-    def back(dense, record):
+    last_k = [None]  # --dump-outputs: the last timed step's K
+
+    def back(dense, record, keep=False):
         if record:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
@@ -428,6 +524,8 @@ def main_c3(args):
         if record:
             ev[1].record()
             (gram_ev if record is True else gram_ev_alone).append(ev)
+        if keep:
+            last_k[0] = K
         return K
 
     def run(steps, record, pipelined):
@@ -435,17 +533,22 @@ def main_c3(args):
         issued on the side stream before step s's Gram, so the latency-bound walks run beside the
         MFMA tiles; every step still runs its whole path, and the call's first front is not
         overlapped (nothing is carried across the call's boundary)."""
+        keep_last = bool(args.dump_outputs) and record is True
+        ahead = RunAhead(main, args.run_ahead)
         if not pipelined:
-            for _ in range(steps):
-                back(front(), record)
+            for s_ in range(steps):
+                back(front(), record, keep_last and s_ + 1 == steps)
+                ahead.step()
             return
         cur = front_on_side()
         for s_ in range(steps):
+            if s_:
+                ahead.step()
             dense, done = cur
             main.wait_event(done)
             dense.record_stream(main)  # (allocated on `side`, read on `main`)
             cur = front_on_side() if s_ + 1 < steps else None
-            back(dense, record)
+            back(dense, record, keep_last and s_ + 1 == steps)
 
     # pipelined by default only while the front is a real share of the step: at C3 (the Gram 0.205 ms, the front
     # ~0.09 ms alone) 0.291-0.301 vs 0.295-0.298 serial; at C2 the front's 800 MB read of W slows the 7.4 ms MFMA
@@ -457,16 +560,22 @@ def main_c3(args):
     run(args.steps, True, pipelined)
     torch.cuda.synchronize()
     t = time.perf_counter() - t0
-    # latency of one un-pipelined step (reported beside the throughput; not part of `value`)
-    run(2, False, False)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    run(5, "alone", False)
-    torch.cuda.synchronize()
-    serial_ms = 1000.0 * (time.perf_counter() - t1) / 5
+    if args.dump_outputs and last_k[0] is not None:
+        dump_matrix(args.dump_outputs, "K", last_k[0][:n, :n])
+    last_k[0] = None
     gram_ms_pipe = float(np.mean([a.elapsed_time(b) for a, b in gram_ev]))
-    # the roofline's time: the Gram alone (the serial steps); pipelined it shares the GPU with the next front
-    gram_ms = float(np.mean([a.elapsed_time(b) for a, b in gram_ev_alone]))
+    serial_ms = None
+    gram_ms = gram_ms_pipe  # (without --full: the Gram's time in the timed steps)
+    if args.full:
+        # latency of one un-pipelined step (reported beside the throughput; not part of `value`)
+        run(2, False, False)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        run(5, "alone", False)
+        torch.cuda.synchronize()
+        serial_ms = 1000.0 * (time.perf_counter() - t1) / 5
+        # the roofline's time: the Gram alone (the serial steps); pipelined it shares the GPU with the next front
+        gram_ms = float(np.mean([a.elapsed_time(b) for a, b in gram_ev_alone]))
     # the symmetric product's unique entries, 2 k flops each (the kernel computes the tiles on and
     # above the diagonal and mirrors them; counting 2 n^2 k would credit work it does not do; k = n,
     # the zero padding of the k range is not counted either)
@@ -475,7 +584,9 @@ def main_c3(args):
     split = prec == "split"
     roof = dense_gram_roofline(prec, flops, gram_ms)
     roof.update({"kernel_ms": gram_ms,
-                 "kernel_ms_note": "HIP events around the Gram in the serial steps (alone on the GPU)",
+                 "kernel_ms_note": ("HIP events around the Gram in the serial steps (alone on the GPU)" if args.full else
+                                    "HIP events around the Gram in the timed steps (--full: re-timed alone in serial "
+                                    "steps)"),
                  "kernel_ms_pipelined": gram_ms_pipe})
     out = {
         "metric": (f"GRF kernel-matrices/sec ({'Cora N=2708' if args.workload == 'c3' else f'ER N={n}'}, dense path, "
@@ -499,7 +610,7 @@ def main_c3(args):
         "pipelined": pipelined,
         "serial_ms_per_step": serial_ms,
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_dense(W, f, m, p, L,
                                                  host_threads())
     print(json.dumps(out), flush=True)
@@ -538,6 +649,17 @@ def main():
     ap.add_argument("--walks", type=int, default=128)
     ap.add_argument("--length", type=int, default=8)
     ap.add_argument("--p-halt", type=float, default=0.1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the in-run K parity check, the serial "
+                         "(un-pipelined) steps with the walk kernel timed alone, the gather roofline's re-timed Gram "
+                         "tiles, the dense-path MFMA legs and the CPU baseline (each still switched off by its own "
+                         "option below); without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / "
+                         "float64; a fixed, seeded sample of outputs too large to keep whole, at most 64 MB in all)")
+    ap.add_argument("--run-ahead", type=int, default=4,
+                    help="steps the host may enqueue ahead of the GPU (default 4; 0 = unbounded: a long run's "
+                         "fronts then outgrow HBM before their steps have run, see RunAhead)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--transfers", action="store_true",
                     help="also time the host hand-over of the drop-in boundary (SURVEY.md §8d: H2D of the CSR "
@@ -756,12 +878,16 @@ def main():
         stream before step s's K assembly, so the two overlap on the GPU; every step still runs
         its whole path, and the first front of the call is not overlapped (no work is carried
         across the call's boundary)."""
+        ahead = RunAhead(main, args.run_ahead)
         if not args.overlap:
             for _ in range(steps):
                 back(front(record_walk), record)
+                ahead.step()
             return
         cur = front_on_side()
         for s_ in range(steps):
+            if s_:
+                ahead.step()  # (after the previous step's K assembly and the front issued with it)
             if pl.mode == "sym":
                 # the next front starts when this step's Gram tiles are done: it runs beside the
                 # HBM-bound mirror instead of the gather-bound Gram
@@ -798,14 +924,21 @@ def main():
     if coll:
         from grf_amd.dist import check_gather_overflow
         check_gather_overflow(dev)  # (raises if a bounded all-gather truncated a rank's Phi)
-    # in-run parity of the LAST TIMED step's K block (the pipelined path itself) against the Phi that
+    if args.dump_outputs:
+        # the last timed step's outputs, before anything below touches K: this rank's K block and (rank 0) the
+        # Phi the step made
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_matrix(args.dump_outputs, "K" + sfx, P.k_view(K, pl), DUMP_MATRIX_BYTES // world)
+        if rank == 0:
+            dump_phi(args.dump_outputs, "phi", P.phi_csr(last[0].phi))
+    # --full: in-run parity of the LAST TIMED step's K block (the pipelined path itself) against the Phi that
     # step gathered (every rank), before the serial steps below overwrite K
-    parity = P.k_block_check(eng, last[0], pl, K)
-    # latency of one un-pipelined step (reported beside the throughput; not part of `value`), with
+    parity = P.k_block_check(eng, last[0], pl, K) if args.full else None
+    # --full: latency of one un-pipelined step (reported beside the throughput; not part of `value`), with
     # the walk kernel timed alone there
     ov = args.overlap
     serial_ms = None
-    if args.serial_steps > 0:
+    if args.full and args.serial_steps > 0:
         args.overlap = False
         run(1, False)  # (warm-up of the serial order)
         torch.cuda.synchronize()
@@ -828,7 +961,7 @@ def main():
                        "k_rows": args.k_rows, "hash": h, "sum": s_}, fh)
     # the sparse Gram tiles' gather roofline (whole-K mode): their bucket-line gathers against the
     # guide's indexed-row rates (after the fingerprint: the timing launches rewrite K's upper tiles)
-    gather_rl = gather_roofline(eng, last[0], pl, K) if pl.mode == "sym" else None
+    gather_rl = gather_roofline(eng, last[0], pl, K) if args.full and pl.mode == "sym" else None
     coll_ms = float(np.mean([a.elapsed_time(b_) for a, b_, _, _ in gather_stats])) if gather_stats else 0.0
     coll_sent = float(np.mean([x for _, _, x, _ in gather_stats])) if gather_stats else 0.0
     coll_recv = float(np.mean([x for _, _, _, x in gather_stats])) if gather_stats else 0.0
@@ -839,14 +972,16 @@ def main():
         dist_all_reduce(tt, op=dist.ReduceOp.MAX)
         t, gram_avg, walk_ms = (float(x) for x in tt.tolist())
         # every rank's Gram time, collective time and volume, and parity ratio (rank order)
-        mine = torch.tensor([float(np.mean(gram_ms)), coll_ms, coll_sent, coll_recv, parity["max_ratio"],
+        mine = torch.tensor([float(np.mean(gram_ms)), coll_ms, coll_sent, coll_recv,
+                             parity["max_ratio"] if parity else 0.0,
                              float(pl.e - pl.b), gram_alone or 0.0, ar_ms, ar_bytes], dtype=torch.float64, device=dev)
         allr = torch.zeros(world * mine.numel(), dtype=torch.float64, device=dev)
         allr[rank * mine.numel():(rank + 1) * mine.numel()] = mine
         dist_all_reduce(allr)
         per_rank = allr.view(world, -1).cpu().numpy()
-        parity = dict(parity, max_ratio=float(per_rank[:, 4].max()), ok=bool(per_rank[:, 4].max() <= 1.0),
-                      per_rank=[float(x) for x in per_rank[:, 4]])
+        if parity is not None:
+            parity = dict(parity, max_ratio=float(per_rank[:, 4].max()), ok=bool(per_rank[:, 4].max() <= 1.0),
+                          per_rank=[float(x) for x in per_rank[:, 4]])
         dist_info = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                      "rank_rows": [int(x) for x in per_rank[:, 5]],
                      "gram_ms_per_rank": [float(x) for x in per_rank[:, 0]],
@@ -983,9 +1118,14 @@ def main():
         "front_at": args.front_at,
         "serial_ms_per_step": serial_ms,
     }
+    out["full"] = bool(args.full)
+    if not args.full:
+        # the walk's time and the K check come from runs of their own (--full); parity, roofline_gather and
+        # serial_ms_per_step are None for the same reason
+        out["roofline_walk"] = out["parity_note"] = None
     if dist_info is not None:
         out["distributed"] = dist_info
-    if headline and not args.no_mfma_leg:
+    if args.full and headline and not args.no_mfma_leg:
         # (side legs: a failure there is reported in the line and never costs the headline number)
         for key, wl in (("roofline_mfma", "c3"), ("roofline_mfma_c2", "c2")):  # C3 (Cora); C2 (ER N = 10k) dense path
             try:
@@ -999,7 +1139,7 @@ def main():
             out["transfers"]["pcie_inclusive_unit"] = unit
         except Exception as exc:  # noqa: BLE001
             out["transfers"] = {"error": f"{type(exc).__name__}: {exc}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(A, f, m, p, L, args.cpu_rows, host_threads(), k_rows=args.k_rows)
             out["cpu_baseline"]["host"] = host_cpu_note()

@@ -275,7 +275,7 @@ def test_dense_path_bench_pipelined_line():
     out = {}
     for flag in ("", "--no-overlap"):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c3", "--steps", "5",
-                            "--warmup", "1", "--no-cpu-baseline"] + ([flag] if flag else []),
+                            "--warmup", "1", "--full", "--no-cpu-baseline"] + ([flag] if flag else []),
                            cwd=root, capture_output=True, text=True, timeout=240)
         assert r.returncode == 0, r.stderr[-2000:]
         out[flag] = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -285,5 +285,3 @@ def test_dense_path_bench_pipelined_line():
         assert d["unit"] == "K-matrices/s" and d["value"] > 0 and d["ms_per_step"] > 0 and d["serial_ms_per_step"] > 0
         rf = d["roofline"]
         assert rf["bound"] == "mfma" and 0 < rf["frac"] < 1 and rf["kernel_ms"] > 0 and rf["kernel_ms_pipelined"] > 0
-
-

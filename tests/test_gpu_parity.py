@@ -1489,7 +1489,7 @@ def test_bench_line_n2_reports_parity_and_collectives_gloo(mode, world):
     env = dict(os.environ, GRF_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--n-nodes", "20000",
+           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--n-nodes", "20000",
            "--edges", "200000", "--mode", mode]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -1571,7 +1571,7 @@ def test_bench_cols_at_headline_size_gloo(eng, world):
         env = dict(os.environ, GRF_DIST_BACKEND="gloo")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-               "--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--rank-turns",
+               "--gpus", str(world), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--rank-turns",
                "--fingerprint-dir", fp_dir]
         r = _run_beating(cmd, root, env, 800, f"c4_gloo_n{world}")
         assert r.returncode == 0, r.stderr[-3000:]
@@ -1697,7 +1697,7 @@ def test_bench_c5_cols_at_size_gloo(eng, world, k_rows):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
                "--workload", "c5", "--k-rows", str(k_rows), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline", "--rank-turns", "--fingerprint-dir", fp_dir]
+               "--full", "--no-cpu-baseline", "--rank-turns", "--fingerprint-dir", fp_dir]
         r = _run_beating(cmd, root, env, 1000, f"c5_gloo_n{world}")
         if r.returncode != 0 and os.environ.get("GRF_TEST_OUT"):
             with open(os.path.join(os.environ["GRF_TEST_OUT"], f"c5_gloo_n{world}.failed.log"), "w") as fh:
@@ -1749,7 +1749,7 @@ def test_bench_allreduce_at_headline_size_gloo():
     env = dict(os.environ, GRF_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--mode", "allreduce", "--steps", "1", "--warmup", "1", "--serial-steps", "0",
+           "--gpus", "2", "--mode", "allreduce", "--steps", "1", "--warmup", "1", "--full", "--serial-steps", "0",
            "--no-cpu-baseline"]
     r = _run_beating(cmd, root, env, 1400, "allreduce_gloo_n2")
     out_dir = os.environ.get("GRF_TEST_OUT")
@@ -1790,7 +1790,7 @@ def test_bench_multi_gpu_path_on_rccl_one_rank(mode):
     env.pop("GRF_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--n-nodes", "20000",
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--n-nodes", "20000",
            "--edges", "200000", "--mode", mode]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]

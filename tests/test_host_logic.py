@@ -443,6 +443,46 @@ def test_gather_model_counts_bucket_line_visits():
             assert got[0] == want_lines and got[1] == want_rec, (unit, sym)
 
 
+def test_bench_dump_helpers_write_fixed_samples(tmp_path):
+    """bench.py --dump-outputs: a matrix within the budget is written whole, a larger one as the sub-matrix of
+    a seeded choice of rows and columns (the same in every call) with the indices beside it; Phi as its row
+    counts and the entries of a seeded choice of rows within the entry budget.  Every file float32 / float64."""
+    import types
+
+    import torch
+
+    import bench
+    d = str(tmp_path)
+    M = torch.arange(1500 * 700, dtype=torch.float32).view(1500, 700)[:, :699]  # (a strided view, as K's is)
+    bench.dump_matrix(d, "small", M[:10])
+    assert np.array_equal(np.load(os.path.join(d, "small.npy")), M[:10].numpy())
+    for name in ("K", "K2"):
+        bench.dump_matrix(d, name, M, budget=1 << 18)
+    s = np.load(os.path.join(d, "K_sample.npy"))
+    ri = np.load(os.path.join(d, "K_sample_rows.npy"))
+    ci = np.load(os.path.join(d, "K_sample_cols.npy"))
+    assert s.dtype == np.float32 and ri.dtype == np.float64 and ci.dtype == np.float64
+    assert s.shape == (1024, 64) and s.nbytes <= 1 << 18
+    assert np.all(np.diff(ri) > 0) and np.all(np.diff(ci) > 0) and ri[-1] < 1500 and ci[-1] < 699
+    assert np.array_equal(s, M.numpy()[np.ix_(ri.astype(int), ci.astype(int))])
+    for part in ("", "_rows", "_cols"):
+        assert np.array_equal(np.load(os.path.join(d, f"K2_sample{part}.npy")),
+                              np.load(os.path.join(d, f"K_sample{part}.npy")))
+    n = 6000
+    cnt = np.random.default_rng(0).integers(0, 40, n)
+    ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    phi = types.SimpleNamespace(n_rows=n, ptr=torch.from_numpy(ptr), idx=torch.arange(ptr[-1], dtype=torch.int32),
+                                val32=-torch.arange(ptr[-1], dtype=torch.float32))
+    bench.dump_phi(d, "phi", phi, budget_entries=5000)
+    assert np.array_equal(np.load(os.path.join(d, "phi_row_counts.npy")), cnt.astype(np.float64))
+    rows = np.load(os.path.join(d, "phi_sample_rows.npy")).astype(int)
+    cols = np.load(os.path.join(d, "phi_sample_cols.npy"))
+    vals = np.load(os.path.join(d, "phi_sample_vals.npy"))
+    assert 0 < len(rows) and np.all(np.diff(rows) > 0) and cols.dtype == np.float64 and vals.dtype == np.float32
+    want = np.concatenate([np.arange(ptr[r_], ptr[r_ + 1]) for r_ in rows])
+    assert len(want) <= 5000 and np.array_equal(cols, want) and np.array_equal(vals, -want.astype(np.float32))
+
+
 def test_hub_column_policy_extension():
     """engine.column_stats: columns in >= share of the rows, in panel widths of 32; with `extend` (the split
     panel's HUB_EXTEND_SHARE) a graph that has a panel at `share` takes its columns down to `extend`, and a

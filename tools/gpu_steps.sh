@@ -8,6 +8,7 @@
 #                                                    space-separated subset of "fetch write sq lds ta")
 #   py:<name>:<seconds>:<python script and args>  -> <tag>/<name>.txt
 #   dist:<name>:<seconds>:<world>:<bench.py args> -> bench.py under torch.distributed.run (gloo, one GPU)
+# (bench.py args: add --full for the whole line -- parity, serial steps, side rooflines, CPU baseline)
 # usage: tools/gpu_steps.sh <tag> <step> [<step> ...]
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-/root/repo}
