@@ -301,6 +301,11 @@ struct CgState {
     int32_t *rhs_zero, *conv;
     uint32_t *ticket;
     int32_t *iters, *done;
+    // Lanczos coefficients (grf_cg_gram_solve_lanczos_f64; NULL otherwise): row k holds iteration k's alpha
+    // per column, row max_iter + k its beta, as stored below (rounded, after the eps / conv guards)
+    double *coef;
+    int64_t ld_coef;
+    int32_t max_iter;
 };
 
 enum CgFinal { kFinNorm = 0, kFinInit = 1, kFinAlpha = 2, kFinUpdate = 3 };
@@ -338,10 +343,13 @@ __device__ inline void cg_final_column(int fin, int c, double s, const CgState &
         else a = st.rr[c] / s;
         if (st.conv[c]) a = 0.0;
         st.alpha[c] = (double)(T)a;
+        if (st.coef) st.coef[(int64_t)(*st.iters) * st.ld_coef + c] = (double)(T)a;
     } else {
         const double old = st.rr[c];
         const double b = old < kCgEps ? 0.0 : s / old;
         st.beta[c] = (double)(T)b;
+        // (*iters is still this iteration's k: thread 0 counts it up after the columns are final)
+        if (st.coef) st.coef[((int64_t)st.max_iter + *st.iters) * st.ld_coef + c] = (double)(T)b;
         st.rr[c] = s;
         const double nrm = st.rhs_zero[c] ? 0.0 : sqrt(s);
         st.rnorm[c] = nrm;
@@ -494,7 +502,8 @@ static int32_t cg_solve_impl(int64_t n_sys, const int64_t *ptr, const int32_t *i
                              const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
                              const float *t_val, double noise, const T *rhs, int64_t ld_rhs, int32_t n_rhs,
                              double tolerance, int32_t max_iter, T *x, int64_t ldx, void *workspace,
-                             size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream) {
+                             size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream,
+                             double *coef = nullptr, int64_t ld_coef = 0) {
     GRF_REQUIRE(n_sys > 0 && n_cols > 0 && ptr && t_ptr && rhs && x, GRF_EINVAL, "grf_cg_gram_solve: bad arguments");
     GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_cg_gram_solve: n_rhs must be in [1, %d]",
                 kMaxRhs);
@@ -514,6 +523,9 @@ static int32_t cg_solve_impl(int64_t n_sys, const int64_t *ptr, const int32_t *i
     st.rhs_zero = q; st.conv = q + Sn;
     st.ticket = (uint32_t *)(q + 2 * Sn); st.iters = q + 2 * Sn + 1; st.done = q + 2 * Sn + 2;
     GRF_CHECK_HIP(hipMemsetAsync(q, 0, (size_t)(2 * Sn + 8) * sizeof(int32_t), sm));
+    st.coef = coef; st.ld_coef = ld_coef; st.max_iter = max_iter;
+    if (coef && max_iter > 0)
+        GRF_CHECK_HIP(hipMemsetAsync(coef, 0, (size_t)2 * max_iter * ld_coef * sizeof(double), sm));
 
     const unsigned rb = (unsigned)std::min<int64_t>(cdiv<int64_t>(n_sys, 4), kRedBlocks);
     const int64_t nel = n_sys * Sn;
@@ -697,6 +709,18 @@ int32_t grf_cg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *
     return cg_solve_impl<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs,
                                  n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
                                  stream);
+}
+
+int32_t grf_cg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                                      const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr,
+                                      const int32_t *t_idx, const float *t_val, double noise, const double *rhs,
+                                      int64_t ld_rhs, int32_t n_rhs, double tolerance, int32_t max_iter, double *x,
+                                      int64_t ldx, void *workspace, size_t workspace_bytes, int32_t *iters_out,
+                                      double *resid_out, double *coef, int64_t ld_coef, grf_stream_t stream) {
+    GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_cg_gram_solve_lanczos_f64: bad coefficient buffer");
+    return cg_solve_impl<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs,
+                                 n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
+                                 stream, coef, ld_coef);
 }
 
 #pragma GCC visibility pop

@@ -18,6 +18,7 @@ Subclasses ``gpytorch.models.ExactGP`` when gpytorch is installed; otherwise a
 import torch
 
 from grf_amd.engine import DeviceCSR, get_engine  # noqa: F401
+from grf_amd.features import grf_marginal_log_likelihood, resolve_cg_tolerance
 
 from ..gptorch_kernels_sparse.sparse_grf_kernel import SparseGRFKernel
 
@@ -60,6 +61,23 @@ class SparseGraphGP(_Base):
             raise ValueError("predict: the step matrices live on another device than x_test")
         return phi
 
+    def marginal_log_likelihood(self, probes=None, n_probes=64, generator=None, tolerance=None, max_iter=1000,
+                                per_datum=True):
+        """The training objective the reference evaluates as ``mll(model(x_train), y_train)`` under
+        ``max_cholesky_size(0)``: the marginal log-likelihood of ``y_train`` (zero mean) by CG and stochastic
+        Lanczos quadrature, K never formed (``grf_amd.features.grf_marginal_log_likelihood``).  A
+        differentiable fp64 scalar: ``backward()`` fills the modulator's gradient and, when the likelihood's
+        noise is a tensor, the noise's (a float noise is a constant).  ``per_datum`` divides by the number
+        of training points, as ``ExactMarginalLogLikelihood`` does."""
+        noise = self.likelihood.noise if hasattr(self.likelihood, "noise") else self.likelihood
+        info = {}
+        out = grf_marginal_log_likelihood(
+            self.covar_module.modulator_vector, noise, self.covar_module._step_set(), self.x_train.int().flatten(),
+            self.y_train, probes=probes, n_probes=n_probes, generator=generator, tolerance=tolerance,
+            max_iter=max_iter, per_datum=per_datum, info=info)
+        self.last_cg_iterations = info["cg_iterations"]
+        return out
+
     @torch.no_grad()
     def predict(self, x_test, n_samples=64, cg_dtype=torch.float64, max_iter=1000, tolerance=None):
         """(n_samples x n_test) posterior samples (float32, like the reference)."""
@@ -74,8 +92,7 @@ class SparseGraphGP(_Base):
         # the reference's draws, same shapes and order (sparse_grf_model.py:36-37)
         eps1_batch = torch.randn(n_samples, self.num_nodes, device=dev)
         eps2_batch = noise_std * torch.randn(n_samples, len(train_indices), device=dev)
-        if tolerance is None:
-            tolerance = gpytorch.settings.cg_tolerance.value() if gpytorch is not None else 1.0
+        tolerance = resolve_cg_tolerance(tolerance)
         out, self.last_cg_iterations = eng.pathwise_predict(
             phi, train_indices.to(eng.device), test_indices.to(eng.device), self.y_train, noise_variance,
             eps1_batch, eps2_batch, tolerance=tolerance, max_iter=max_iter, dtype=cg_dtype)

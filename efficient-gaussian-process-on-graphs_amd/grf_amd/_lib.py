@@ -26,7 +26,7 @@ RNG_PCG64, RNG_PHILOX = 0, 1
 LOAD_CUMULATIVE, LOAD_NONCUMULATIVE, LOAD_ABLATION = 0, 1, 2
 NORM_DIV, NORM_MUL_RECIP = 0, 1
 REC_LINE, REC_PACKED, REC_SLOT = 128, 12, 32
-ABI_VERSION = 8  # include/grf.h GRF_ABI_VERSION: argument lists change between revisions
+ABI_VERSION = 9  # include/grf.h GRF_ABI_VERSION: argument lists change between revisions
 
 
 class GrfWalkParams(ctypes.Structure):
@@ -113,6 +113,12 @@ SIGNATURES = {
     "grf_cg_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "grf_cg_gram_solve": (_i32, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _dbl, _vp, _i64, _i32, _dbl, _i32,
                                  _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    # the matrix-free marginal likelihood: CG with its Lanczos coefficients, the modulator gradient's contraction
+    "grf_cg_gram_solve_lanczos_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _dbl, _vp, _i64, _i32,
+                                             _dbl, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp, _i64, _vp]),
+    "grf_steps_frob_f64": (_i32, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp,
+                                  _sz, _vp]),
+    "grf_steps_frob_workspace_bytes": (_sz, [_i64, _i32]),
     "grf_gram_sparse_kslice": (_i32, [_i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
                                       _i64, _vp, _sz, _vp]),
     "grf_gram_dense": (_i32, [_i64, _i64, _vp, _i64, _vp, _i64, _vp]),

@@ -1045,31 +1045,131 @@ class GRFEngine:
         return Y
 
     def cg_solve(self, phi: DeviceCSR, B: torch.Tensor, noise: float, rows=None, phi_t: Optional[DeviceCSR] = None,
-                 tolerance: float = 1.0, max_iter: int = 1000, return_residuals: bool = False):
+                 tolerance: float = 1.0, max_iter: int = 1000, return_residuals: bool = False,
+                 return_lanczos: bool = False):
         """linear_cg on (Phi[rows] Phi[rows]^T + noise I) X = B for the columns of B (n x S, S <= 256).
 
         B float64 runs the recurrence in fp64, float32 in the reference's fp32.  Returns
         (X, iterations) [+ the final residual norms of the normalised columns].  tolerance / max_iter default to gpytorch's settings.cg_tolerance (1)
-        and settings.max_cg_iterations (1000)."""
+        and settings.max_cg_iterations (1000).  return_lanczos (fp64 only) appends the CG coefficients, a
+        (2 max_iter x S) fp64 device tensor: row k holds alpha_k of every column, row max_iter + k its
+        beta_k, zero for the iterations that did not run (the Lanczos tridiagonals come from these)."""
         rmap = self._row_map(rows)
         n_sys = phi.n_rows if rmap is None else rmap.numel()
         if B.dtype not in (torch.float32, torch.float64) or B.dim() != 2 or B.stride(1) != 1 \
                 or B.shape[0] != n_sys:
             raise ValueError("cg_solve: B must be a float32/float64 (n_rows x S) row-major matrix")
+        if return_lanczos and B.dtype != torch.float64:
+            raise ValueError("cg_solve: return_lanczos needs a float64 B")
         phi_t = self.csr_transpose(phi, rmap) if phi_t is None else phi_t
         S = B.shape[1]
         X = torch.empty((n_sys, S), dtype=B.dtype, device=self.device)
         ws = self._ws(self.lib.grf_cg_workspace_bytes(n_sys, phi.n_cols, S))
         iters = ctypes.c_int32(0)
         resid = np.zeros(S, np.float64)
-        fn = self.lib.grf_cg_gram_solve if B.dtype == torch.float32 else self.lib.grf_cg_gram_solve_f64
-        C.check(fn(n_sys, _p(phi.ptr), _p(phi.idx), _p(phi.val32), _p(rmap), phi.n_cols, _p(phi_t.ptr),
-                   _p(phi_t.idx), _p(phi_t.val32), float(noise), _p(B), B.stride(0), S, float(tolerance),
-                   int(max_iter), _p(X), X.stride(0), _p(ws), ws.numel(), ctypes.byref(iters),
-                   resid.ctypes.data_as(ctypes.c_void_p), self.stream), "grf_cg_gram_solve")
-        if return_residuals:
-            return X, int(iters.value), resid
-        return X, int(iters.value)
+        head = (n_sys, _p(phi.ptr), _p(phi.idx), _p(phi.val32), _p(rmap), phi.n_cols, _p(phi_t.ptr),
+                _p(phi_t.idx), _p(phi_t.val32), float(noise), _p(B), B.stride(0), S, float(tolerance),
+                int(max_iter), _p(X), X.stride(0), _p(ws), ws.numel(), ctypes.byref(iters),
+                resid.ctypes.data_as(ctypes.c_void_p))
+        coef = None
+        if return_lanczos:
+            coef = torch.empty((2 * max(int(max_iter), 0), S), dtype=torch.float64, device=self.device)
+            C.check(self.lib.grf_cg_gram_solve_lanczos_f64(*head, _p(coef), S, self.stream),
+                    "grf_cg_gram_solve_lanczos_f64")
+        else:
+            fn = self.lib.grf_cg_gram_solve if B.dtype == torch.float32 else self.lib.grf_cg_gram_solve_f64
+            C.check(fn(*head, self.stream), "grf_cg_gram_solve")
+        out = (X, int(iters.value)) + ((resid,) if return_residuals else ()) + ((coef,) if return_lanczos else ())
+        return out
+
+    # ------------------------------------- matrix-free marginal likelihood (CG + stochastic Lanczos quadrature)
+    def steps_frob(self, steps, rows, A: torch.Tensor, WA: torch.Tensor, B: torch.Tensor, WB: torch.Tensor,
+                   wt: torch.Tensor, n_steps: Optional[int] = None) -> torch.Tensor:
+        """out[l] = sum_c wt[c] sum_r (A[r,c] (M_l[rows[r]] WB)[c] + B[r,c] (M_l[rows[r]] WA)[c]) for the first
+        n_steps (default: all) step matrices of ``steps`` (a features.StepMatrices): (L,) fp64 on the device.
+        A, B: (len(rows) x S), WA, WB: (n_cols x S), fp64 row-major, S <= 256 (grf_steps_frob_f64)."""
+        rmap = self._row_map(rows)
+        n_sel = steps.shape[0] if rmap is None else rmap.numel()
+        L = steps.L if n_steps is None else int(n_steps)
+        if not 1 <= L <= steps.L:
+            raise ValueError("steps_frob: n_steps must be in [1, L]")
+        if A.dim() != 2 or A.shape[0] != n_sel or B.shape != A.shape or WA.dim() != 2 or WB.shape != WA.shape \
+                or WA.shape != (steps.shape[1], A.shape[1]):
+            raise ValueError("steps_frob: A, B must be (rows x S) and WA, WB (n_cols x S)")
+        if wt.numel() != A.shape[1]:
+            raise ValueError("steps_frob: wt must hold one weight per column")
+        A, B, WA, WB, wt = (t.to(self.device, torch.float64).contiguous() for t in (A, B, WA, WB, wt.flatten()))
+        S = A.shape[1]
+        out = self._empty(L, torch.float64)
+        ws = self._ws(self.lib.grf_steps_frob_workspace_bytes(n_sel, L))
+        sp = steps._ptrs
+        C.check(self.lib.grf_steps_frob_f64(n_sel, L, sp[0], sp[1], sp[2], _p(rmap), _p(A), _p(B), max(S, 1), _p(WA),
+                                            _p(WB), max(S, 1), _p(wt), S, _p(out), _p(ws), ws.numel(), self.stream),
+                "grf_steps_frob_f64")
+        return out
+
+    @staticmethod
+    def slq_logdet(coef: np.ndarray, iters: int, sq_norms: np.ndarray) -> float:
+        """Stochastic Lanczos quadrature from CG coefficients: coef (2 max_iter x t) holds the probe columns'
+        alpha rows then beta rows (cg_solve(return_lanczos=True)), sq_norms their ||z_i||^2.  Column c's
+        tridiagonal covers its first m_c iterations (up to its first zero alpha, or all that ran):
+        T[k,k] = 1/alpha_k + beta_{k-1}/alpha_{k-1}, T[k,k+1] = sqrt(beta_k)/alpha_k, and
+        log det ~ (1/t) sum_i ||z_i||^2 sum_j V_i[0,j]^2 log lambda_ij.  Host fp64: t small eigenproblems."""
+        max_iter, t = coef.shape[0] // 2, coef.shape[1]
+        total = 0.0
+        for c in range(t):
+            a, b = coef[:iters, c], coef[max_iter:max_iter + iters, c]
+            zero = np.flatnonzero(a == 0.0)
+            m = int(zero[0]) if zero.size else int(iters)
+            if m == 0:
+                continue
+            T = np.zeros((m, m))
+            d = 1.0 / a[:m]
+            d[1:] += b[:m - 1] / a[:m - 1]
+            T[np.arange(m), np.arange(m)] = d
+            off = np.sqrt(b[:m - 1]) / a[:m - 1]
+            T[np.arange(m - 1), np.arange(1, m)] = off
+            T[np.arange(1, m), np.arange(m - 1)] = off
+            lam, V = np.linalg.eigh(T)
+            total += float(sq_norms[c]) * float(np.sum(V[0] ** 2 * np.log(lam)))
+        return total / t
+
+    def marginal_log_likelihood(self, steps, f: torch.Tensor, train_idx, y: torch.Tensor, noise: float,
+                                probes: torch.Tensor, tolerance: float = 1.0, max_iter: int = 1000):
+        """MLL(f, s2) = -1/2 y^T K^-1 y - 1/2 log det K^ - n/2 log 2 pi with K^ = Phi_T Phi_T^T + s2 I,
+        Phi = sum_l f_l M_l, and its gradient, K never formed (fp64): one CG solve of [y | Z] for the
+        probes Z (n_train x t, t <= 255), log det by stochastic Lanczos quadrature from the solve's own
+        coefficients, the gradients by gpytorch's estimators
+            1/2 a^T dK a - 1/(2t) sum_i u_i^T dK z_i,   a = K^-1 y, u_i = K^-1 z_i.
+        Returns (value (float), d/df ((min(len(f), L),) fp64 device tensor), d/ds2 (float), CG iterations)."""
+        tr = self._row_map(train_idx)
+        n = tr.numel()
+        yv = y.detach().to(self.device, torch.float64).flatten()
+        if probes.dim() != 2 or probes.shape[0] != n or yv.numel() != n:
+            raise ValueError("marginal_log_likelihood: probes must be (n_train x t) and y (n_train,)")
+        t = probes.shape[1]
+        if not 1 <= t <= 255:
+            raise ValueError("marginal_log_likelihood: between 1 and 255 probes per call")
+        rhs = torch.cat([yv[:, None], probes.detach().to(self.device, torch.float64)], dim=1).contiguous()
+        phi = steps.phi(f)
+        phi_t = self.csr_transpose(phi, tr)
+        X, iters, coef = self.cg_solve(phi, rhs, noise, tr, phi_t, tolerance, max_iter, return_lanczos=True)
+        # the weighted column sums both scalars need, one host read with the coefficients' probe columns
+        wt = torch.full((1 + t,), -0.5 / t, dtype=torch.float64, device=self.device)
+        wt[0] = 0.5
+        cols = torch.stack([(rhs * X).sum(0), (X * X).sum(0), (rhs * rhs).sum(0)]).cpu().numpy()
+        logdet = self.slq_logdet(coef[:, 1:].cpu().numpy(), iters, cols[2, 1:])
+        value = -0.5 * cols[0, 0] - 0.5 * logdet - 0.5 * n * float(np.log(2.0 * np.pi))
+        # d/ds2: dK = I -> 1/2 a.a - 1/(2t) sum_i u_i.z_i
+        g_noise = 0.5 * cols[1, 0] - 0.5 / t * float(cols[0, 1:].sum())
+        # d/df_l: dK = M_l[T] Phi_T^T + Phi_T M_l[T]^T; the y column pairs a with itself
+        Bm = rhs
+        Bm[:, 0] = X[:, 0]
+        WX = self.spmm(phi_t, X)
+        WB = self.spmm(phi_t, Bm)
+        n_f = min(int(f.numel()), steps.L)
+        g_f = self.steps_frob(steps, tr, X, WX, Bm, WB, wt, n_steps=n_f)
+        return float(value), g_f, float(g_noise), iters
 
     def pathwise_predict(self, phi: DeviceCSR, train_idx, test_idx, y_train: torch.Tensor, noise: float,
                          eps1: torch.Tensor, eps2: torch.Tensor, tolerance: float = 1.0, max_iter: int = 1000,

@@ -256,6 +256,80 @@ def grf_kernel(f: torch.Tensor, steps: StepMatrices, x1=None, x2=None, diag: boo
     return GRFKernelFunction.apply(f, steps, x1, x2, diag)
 
 
+class GRFMarginalLikelihoodFunction(torch.autograd.Function):
+    """The matrix-free marginal log-likelihood of y under K^ = Phi(f)[T] Phi(f)[T]^T + noise I
+    (``GRFEngine.marginal_log_likelihood``: CG + stochastic Lanczos quadrature, fp64, K never formed),
+    differentiable w.r.t. the modulator f and the noise.  The forward computes the value and both
+    gradients (they share the one CG solve); the backward scales them by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, f: torch.Tensor, noise: torch.Tensor, steps: StepMatrices, train_idx, y, probes,
+                tolerance: float, max_iter: int, info: Optional[dict]):
+        eng = steps.engine
+        value, g_f, g_noise, iters = eng.marginal_log_likelihood(
+            steps, f, train_idx, y, float(noise.detach().reshape(-1)[0].item()), probes, tolerance, max_iter)
+        grad_f = torch.zeros(f.numel(), dtype=torch.float64, device=eng.device)
+        grad_f[:g_f.numel()] = g_f  # (modulator entries past the last step matrix do not enter Phi)
+        ctx.grad_f = grad_f.reshape(f.shape).to(device=f.device, dtype=f.dtype)
+        ctx.grad_noise = torch.full(noise.shape, g_noise, dtype=noise.dtype, device=noise.device)
+        if info is not None:
+            info["cg_iterations"] = iters
+        return torch.tensor(value, dtype=torch.float64, device=f.device)
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):
+        gf = ctx.grad_f * g.to(device=ctx.grad_f.device, dtype=ctx.grad_f.dtype)
+        gn = ctx.grad_noise * g.to(device=ctx.grad_noise.device, dtype=ctx.grad_noise.dtype)
+        return gf, gn, None, None, None, None, None, None, None
+
+
+def resolve_cg_tolerance(tolerance: Optional[float]) -> float:
+    """None -> gpytorch.settings.cg_tolerance when gpytorch is installed, else its default 1.0 (the one rule of
+    SparseGraphGP.predict and the marginal likelihood)."""
+    if tolerance is not None:
+        return float(tolerance)
+    try:
+        import gpytorch
+    except ImportError:
+        return 1.0
+    return float(gpytorch.settings.cg_tolerance.value())
+
+
+def grf_marginal_log_likelihood(f: torch.Tensor, noise, steps: StepMatrices, train_idx, y, probes=None,
+                                n_probes: int = 64, generator=None, tolerance: Optional[float] = None,
+                                max_iter: int = 1000, per_datum: bool = True,
+                                info: Optional[dict] = None) -> torch.Tensor:
+    """MLL(f, noise) of y at the training nodes, a differentiable fp64 scalar (on f's device).
+
+    f, noise: torch tensors (noise with one element; a float is a constant) -- the gradient flows to
+    whatever they were computed from.  probes: (n_train x t) Hutchinson probes, t <= 255; by default
+    ``torch.randn(n_train, n_probes, generator=generator)`` drawn on the generator's device, or on the
+    engine's when there is none (no host draw and upload per training step).  per_datum divides by n_train,
+    as gpytorch's ExactMarginalLogLikelihood does.  info: a dict that receives ``cg_iterations``."""
+    eng = steps.engine
+    idx = torch.as_tensor(train_idx).flatten()
+    n = idx.numel()
+    yt = torch.as_tensor(y).flatten()
+    if n == 0 or yt.numel() != n:
+        raise ValueError("grf_marginal_log_likelihood: y must hold one value per training node")
+    if probes is None:
+        if not 1 <= int(n_probes) <= 255:
+            raise ValueError("grf_marginal_log_likelihood: between 1 and 255 probes per call")
+        probes = torch.randn(n, int(n_probes), generator=generator,
+                             device=generator.device if generator is not None else eng.device)
+    elif probes.dim() != 2 or probes.shape[0] != n:
+        raise ValueError(f"grf_marginal_log_likelihood: probes must be ({n} x t), got {tuple(probes.shape)}")
+    elif not 1 <= probes.shape[1] <= 255:
+        raise ValueError("grf_marginal_log_likelihood: between 1 and 255 probes per call")
+    if not torch.is_tensor(noise):
+        noise = torch.tensor(float(noise), dtype=torch.float64)
+    if noise.numel() != 1:
+        raise ValueError("grf_marginal_log_likelihood: noise must have one element")
+    out = GRFMarginalLikelihoodFunction.apply(f, noise, steps, idx, yt, probes, resolve_cg_tolerance(tolerance),
+                                              int(max_iter), info)
+    return out / n if per_datum else out
+
+
 def feature_matrix(f: torch.Tensor, steps: StepMatrices) -> torch.Tensor:
     """Phi as a torch sparse CSR tensor (float32 values, int64 indices) on the device (not differentiable)."""
     phi = steps.phi(f)

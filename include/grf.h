@@ -70,8 +70,9 @@ enum grf_norm {
 
 /* The ABI revision of this header: grf_version() returns it, and a binding must refuse a library whose
  * revision differs (argument lists, or -- ABI 7 -- the GRF_RNG_PHILOX stream, change between revisions;
- * ABI 8 added grf_phi_row_shifts_padded and grf_gram_sparse_cols_padded). */
-#define GRF_ABI_VERSION 8
+ * ABI 8 added grf_phi_row_shifts_padded and grf_gram_sparse_cols_padded; ABI 9 the marginal likelihood's
+ * grf_cg_gram_solve_lanczos_f64 and grf_steps_frob_f64). */
+#define GRF_ABI_VERSION 9
 
 const char *grf_last_error(void);
 int32_t grf_version(void);
@@ -555,6 +556,38 @@ int32_t grf_cg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *
                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream);
 /* (covers both precisions) */
 size_t grf_cg_workspace_bytes(int64_t n_sys, int64_t n_cols, int32_t n_rhs);
+
+/* ------------------------------------------- matrix-free marginal likelihood (training)
+ * MLL(f, s2) = -1/2 y^T K^-1 y - 1/2 log det K^ - n/2 log 2 pi with K^ = Phi_T Phi_T^T + s2 I, estimated
+ * the way the reference trains (gpytorch under max_cholesky_size = 0: CG + stochastic Lanczos
+ * quadrature): one CG solve of [y | Z] whose per-column coefficients give the Lanczos tridiagonals,
+ * and the modulator gradient by the contraction below.  K is never formed. */
+
+/* grf_cg_gram_solve_f64 (same solve: x, *iters_out and resid_out are bit-identical) that also
+ * records the CG coefficients of every iteration k that ran: coef[k * ld_coef + c] = alpha_k and
+ * coef[(max_iter + k) * ld_coef + c] = beta_k of column c, as the recurrence used them (alpha = 0
+ * where p.Ap < eps or the column had converged; beta = 0 where the old r.r < eps).  coef: device,
+ * 2 * max_iter rows of ld_coef >= n_rhs doubles, zeroed first.  Same workspace as the plain solve. */
+int32_t grf_cg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                                      const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr,
+                                      const int32_t *t_idx, const float *t_val, double noise, const double *rhs,
+                                      int64_t ld_rhs, int32_t n_rhs, double tolerance, int32_t max_iter, double *x,
+                                      int64_t ldx, void *workspace, size_t workspace_bytes, int32_t *iters_out,
+                                      double *resid_out, double *coef, int64_t ld_coef, grf_stream_t stream);
+
+/* out[l] = sum_c wt[c] sum_r ( A[r,c] (M_l[row_map[r]] WB)[c] + B[r,c] (M_l[row_map[r]] WA)[c] ), l < L:
+ * the step matrices' rows (step_* are HOST arrays of L <= 64 device pointers, as in
+ * grf_phi_steps_csr_*) times the dense WA / WB (n_cols x ldw, fp64), contracted with A / B
+ * (n_sel x ld, fp64) and the column weights wt[n_rhs]; n_rhs in [1, 256]; row_map int32 or NULL.
+ * With A = K^-1 [y | Z], WA = Phi_T^T A and the same for B = [K^-1 y | Z] this is
+ * sum_c wt[c] a_c^T (dK^/df_l) b_c.  One launch for all steps, the n_sel x n_rhs products never
+ * stored; fp64 sums in a fixed order (two calls give the same bits).  out: L doubles (device). */
+int32_t grf_steps_frob_f64(int64_t n_sel, int32_t L, const int64_t *const *step_ptr, const int32_t *const *step_idx,
+                           const float *const *step_val, const int32_t *row_map, const double *A, const double *B,
+                           int64_t ld, const double *WA, const double *WB, int64_t ldw, const double *wt,
+                           int32_t n_rhs, double *out, void *workspace, size_t workspace_bytes,
+                           grf_stream_t stream);
+size_t grf_steps_frob_workspace_bytes(int64_t n_sel, int32_t L);
 
 /* ------------------------------------------- the GPyTorch surface's feature algebra
  * Device-resident step matrices (one CSR per step: int64 row pointers, sorted int32 columns,
