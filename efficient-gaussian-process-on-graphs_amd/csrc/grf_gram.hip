@@ -888,20 +888,6 @@ __global__ __launch_bounds__(256) void densify_padded_kernel(int64_t cap, const 
     for (int t = tid; t < q4; t += 256) o[t] = reinterpret_cast<const float4 *>(row)[t];
 }
 
-// grf_gram_dense.hip: the dense path's MFMA Gram
-size_t dense_gram_workspace_bytes(int64_t n, int64_t k_dim);
-size_t dense_gram_split_workspace_bytes(int64_t n, int64_t k_dim);
-int32_t dense_gram_split(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
-                         void *workspace, size_t workspace_bytes, bool upper_only, grf_stream_t stream);
-int32_t dense_gram(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk, void *workspace,
-                   size_t workspace_bytes, bool upper_only, grf_stream_t stream);
-int64_t planes_row_bytes(int64_t k_dim);
-int32_t split_planes(int64_t n, int64_t k_dim, const float *A, int64_t lda, void *P, int64_t ldp, grf_stream_t stream);
-int32_t densify_padded_planes(int64_t n_rows, int64_t cap, int64_t n_cols, const int32_t *cnt, const int32_t *idx,
-                              const float *val, void *P, int64_t ldp, grf_stream_t stream);
-int32_t dense_gram_planes(int64_t n, int64_t k_dim, const void *P, int64_t ldp, float *K, int64_t ldk,
-                          void *workspace, size_t workspace_bytes, grf_stream_t stream);
-
 }  // namespace grf
 
 using namespace grf;
@@ -1299,64 +1285,6 @@ int32_t grf_gram_mirror(int64_t n, float *K, int64_t ldk, int64_t max_workgroups
     gram_mirror_swz_kernel<<<(unsigned)grid, 256, 0, S(stream)>>>(n, nt, blocks, K, ldk);
     GRF_CHECK_LAUNCH("gram_mirror_swz_kernel");
     return GRF_OK;
-}
-
-size_t grf_gram_dense_workspace_bytes(int64_t n, int64_t k_dim) { return grf::dense_gram_workspace_bytes(n, k_dim); }
-
-// the MFMA Gram (grf_gram_dense.hip): tiles on and above the diagonal written to both triangles
-// (upper_only: the tiles' K[row][col] only, the seed of the hub-column split's sparse tiles)
-static int32_t gram_dense_impl(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
-                               void *workspace, size_t workspace_bytes, bool upper_only, grf_stream_t stream) {
-    return grf::dense_gram(n, k_dim, A, lda, K, ldk, workspace, workspace_bytes, upper_only, stream);
-}
-
-int32_t grf_gram_dense_ws(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
-                          void *workspace, size_t workspace_bytes, grf_stream_t stream) {
-    return gram_dense_impl(n, k_dim, A, lda, K, ldk, workspace, workspace_bytes, false, stream);
-}
-
-int32_t grf_gram_dense_upper(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
-                             grf_stream_t stream) {
-    return gram_dense_impl(n, k_dim, A, lda, K, ldk, nullptr, 0, true, stream);
-}
-
-int32_t grf_gram_dense(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
-                       grf_stream_t stream) {
-    return grf_gram_dense_ws(n, k_dim, A, lda, K, ldk, nullptr, 0, stream);
-}
-
-size_t grf_gram_dense_split_workspace_bytes(int64_t n, int64_t k_dim) {
-    return grf::dense_gram_split_workspace_bytes(n, k_dim);
-}
-
-// the same K on the bf16 matrix cores: A split exactly into three bf16 planes, six products per term
-int32_t grf_gram_dense_split(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
-                             void *workspace, size_t workspace_bytes, grf_stream_t stream) {
-    GRF_REQUIRE(workspace, GRF_EINVAL, "grf_gram_dense_split: workspace required");
-    return grf::dense_gram_split(n, k_dim, A, lda, K, ldk, workspace, workspace_bytes, false, stream);
-}
-
-// grf_gram_dense_upper on the split products (the hub-column split's panel)
-int32_t grf_gram_dense_split_upper(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
-                                   grf_stream_t stream) {
-    return grf::dense_gram_split(n, k_dim, A, lda, K, ldk, nullptr, 0, true, stream);
-}
-
-int64_t grf_planes_row_bytes(int64_t k_dim) { return grf::planes_row_bytes(k_dim); }
-
-int32_t grf_split_planes(int64_t n, int64_t k_dim, const float *A, int64_t lda, void *P, int64_t ldp,
-                         grf_stream_t stream) {
-    return grf::split_planes(n, k_dim, A, lda, P, ldp, stream);
-}
-
-int32_t grf_densify_padded_planes(int64_t n_rows, int64_t cap, int64_t n_cols, const int32_t *cnt, const int32_t *idx,
-                                  const float *val, void *P, int64_t ldp, grf_stream_t stream) {
-    return grf::densify_padded_planes(n_rows, cap, n_cols, cnt, idx, val, P, ldp, stream);
-}
-
-int32_t grf_gram_dense_planes(int64_t n, int64_t k_dim, const void *P, int64_t ldp, float *K, int64_t ldk,
-                              void *workspace, size_t workspace_bytes, grf_stream_t stream) {
-    return grf::dense_gram_planes(n, k_dim, P, ldp, K, ldk, workspace, workspace_bytes, stream);
 }
 
 int32_t grf_densify_padded(int64_t n_rows, int64_t cap, int64_t n_cols, const int32_t *cnt, const int32_t *idx,

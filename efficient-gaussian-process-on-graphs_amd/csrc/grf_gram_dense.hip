@@ -50,6 +50,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int kTile = 128;  // tile edge (rows and columns)
+constexpr int kBK = 16;     // floats of k per k-tile (the 16 x 16 x 4 blocks and other BK: round 4, removed)
 
 struct DenseArgs {
     const float *A;
@@ -67,15 +68,11 @@ struct DenseArgs {
     int32_t xcd_slots;  // wide kernels: number the slots XCD-contiguously (grid a multiple of 8)
 };
 
-// Fragment layout of one wave's 64 x 64 quarter.
-template <int MF, int BK>
-struct Layout;
-
-template <int BK>
-struct Layout<32, BK> {  // 2 x 2 blocks of 32 x 32; lane (r = lane & 31, h = lane >> 5)
-    static constexpr int NBLK = 2, GG = BK / 8;  // blocks per side; fragment groups per k-tile
+// Fragment layout of one wave's 64 x 64 quarter: 2 x 2 blocks of 32 x 32; lane (r = lane & 31, h = lane >> 5)
+struct Layout {
+    static constexpr int NBLK = 2, GG = kBK / 8;  // blocks per side; fragment groups per k-tile
     typedef f32x16 acc_t;
-    static constexpr int C = BK / 4;  // 16-B chunks per LDS row
+    static constexpr int C = kBK / 4;  // 16-B chunks per LDS row
     static __device__ __forceinline__ int swz(int row) { return (row / (16 / C)) & (C - 1); }
     // LDS float offset of block x's fragment, group g, in an operand image whose quarter starts at row q0
     static __device__ __forceinline__ int off(int q0, int x, int g, int lane) {
@@ -102,11 +99,13 @@ struct Layout<32, BK> {  // 2 x 2 blocks of 32 x 32; lane (r = lane & 31, h = la
     static __device__ __forceinline__ int col(int j, int lane) { return 32 * ((j >> 2) & 1) + (lane & 31); }
 };
 
-template <int BK>
 struct Stage {
-    static constexpr int F = kTile * BK;          // floats per operand per stage
-    static constexpr int PW = kTile * BK / 1024;  // 1-KiB DMA pieces per wave per operand (4 waves)
+    static constexpr int F = kTile * kBK;          // floats per operand per stage
+    static constexpr int PW = kTile * kBK / 1024;  // 1-KiB DMA pieces per wave per operand (4 waves)
 };
+using L = Layout;
+using St = Stage;
+typedef f32x16 Acc[L::NBLK][L::NBLK];  // one wave's quarter: the accumulators of its 2 x 2 blocks
 
 __device__ __forceinline__ void dma16(const float *src, float *lds_piece) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
@@ -148,13 +147,10 @@ __device__ __forceinline__ void tile_coords(int64_t b, int64_t nt, int64_t &bi, 
 
 // The k-loop over [kb, ke) of one tile.  DIAG: B = A (one operand staged).  LIVE: this wave computes
 // (a dead wave still stages its share of the DMA and joins the barriers).
-template <int MF, int BK, int NST, bool DIAG, bool LIVE>
+template <int NST, bool DIAG, bool LIVE>
 __device__ __forceinline__ void kloop(float *lds, const float *const *srcA, const float *const *srcB, int64_t kb,
-                                      int64_t ke, int wave, const int *aoff, const int *boff,
-                                      typename Layout<MF, BK>::acc_t (&c)[Layout<MF, BK>::NBLK][Layout<MF, BK>::NBLK]) {
-    using L = Layout<MF, BK>;
-    using St = Stage<BK>;
-    constexpr int NB = L::NBLK, GG = L::GG;
+                                      int64_t ke, int wave, const int *aoff, const int *boff, Acc &c) {
+    constexpr int NB = L::NBLK, GG = L::GG, BK = kBK;
     static_assert(NB == 2 && GG == 2, "the step sequence below is written for 2 x 2 blocks and 2 groups per k-tile");
     constexpr int D = NST - 2;  // k-tiles in flight behind the one being published
     static_assert(D >= 1 && D <= 3, "the pipelined k-loop needs 3 <= NST <= 5");
@@ -262,12 +258,8 @@ __device__ __forceinline__ void kloop(float *lds, const float *const *srcA, cons
 // K[col][row] (a lane's float4 j holds 4 consecutive rows of one column: one 16-B store mirrored).
 // diag: the quarter straddles the diagonal (a diagonal tile): only entries with col >= row are written
 // (each to both places).  upper: K[row][col] only (the whole quarter, nothing mirrored).
-template <int MF, int BK>
-__device__ __forceinline__ void write_quarter(const DenseArgs &a,
-                                              const typename Layout<MF, BK>::acc_t (&c)[Layout<MF, BK>::NBLK]
-                                                                                       [Layout<MF, BK>::NBLK],
-                                              int64_t r0, int64_t c0, bool diag, bool upper, int lane) {
-    using L = Layout<MF, BK>;
+__device__ __forceinline__ void write_quarter(const DenseArgs &a, const Acc &c, int64_t r0, int64_t c0, bool diag,
+                                              bool upper, int lane) {
     const int64_t n = a.n, ldk = a.ldk;
     float *K = a.K;
 #pragma unroll
@@ -296,29 +288,36 @@ __device__ __forceinline__ void write_quarter(const DenseArgs &a,
     }
 }
 
-// One wave's part of tile `tile` over the k range [kb, ke): its quarter (rows qr.., cols qc..), whether it
-// lies below the diagonal, and the accumulators (zeroed here).
+// One wave's part of a work item: its quarter (rows qr.., cols qc.. of K), whether that straddles the diagonal
+// (only its entries with col >= row are written) or lies wholly below it (nothing computed, nothing mirrored).
 struct Quarter {
     int64_t qr, qc;
     bool diag, below;
+    // this wave's quarter: no MFMAs when it lies wholly below the diagonal or past n
+    __device__ __forceinline__ bool live(int64_t n) const { return !below && qr < n && qc < n; }
 };
 
-template <int MF, int BK, int NST>
-__device__ __forceinline__ Quarter tile_compute(const DenseArgs &a, float *lds, int64_t tile, int64_t kb, int64_t ke,
-                                                int wave, int lane,
-                                                typename Layout<MF, BK>::acc_t (&c)[Layout<MF, BK>::NBLK]
-                                                                                   [Layout<MF, BK>::NBLK]) {
-    using L = Layout<MF, BK>;
-    using St = Stage<BK>;
-    constexpr int NB = L::NBLK;
-    const int wm = wave >> 1, wn = wave & 1;
-    int64_t bi, bj;
-    tile_coords(tile, a.nt, bi, bj);
-    const int64_t m0 = bi * kTile, n0 = bj * kTile;
-    const bool diag = bi == bj;
-    // per-lane DMA sources: piece j of this wave covers LDS chunks p = (wave * PW + j) * 64 + lane,
-    // i.e. row p / C, stored chunk p % C, which holds logical chunk (p % C) ^ swz(row)
-    const float *srcA[St::PW], *srcB[St::PW];
+// the quarter of wave (wm, wn) = (wave >> 1, wave & 1) of an item whose A rows start at m0 and B rows at n0 (a tile:
+// wm 0..1, a wide item: 0..3); in an item above the diagonal every wave has qc > qr
+__device__ __forceinline__ Quarter quarter_of(int64_t m0, int64_t n0, int wm, int wn) {
+    const int64_t R = m0 + wm * 64, Cc = n0 + wn * 64;
+    return Quarter{R, Cc, R == Cc, R > Cc};
+}
+
+// float offsets of block 0's fragment per group in the A and the B image (block x: + x XSTRIDE bytes)
+__device__ __forceinline__ void frag_offsets(int wm, int wn, int lane, int (&aoff)[L::GG], int (&boff)[L::GG]) {
+#pragma unroll
+    for (int g = 0; g < L::GG; ++g) {
+        aoff[g] = L::off(wm * 64, 0, g, lane);
+        boff[g] = L::off(wn * 64, 0, g, lane);
+    }
+}
+
+// Per-lane DMA sources of a tile's fp32 operands (A rows m0.., B rows n0..): piece j of this wave covers LDS
+// chunks p = (wave * PW + j) * 64 + lane, i.e. row p / C, stored chunk p % C, which holds logical chunk
+// (p % C) ^ swz(row)
+__device__ __forceinline__ void tile_sources(const DenseArgs &a, int64_t m0, int64_t n0, int wave, int lane,
+                                             const float *(&srcA)[St::PW], const float *(&srcB)[St::PW]) {
 #pragma unroll
     for (int j = 0; j < St::PW; ++j) {
         const int p = (wave * St::PW + j) * 64 + lane;
@@ -329,26 +328,48 @@ __device__ __forceinline__ Quarter tile_compute(const DenseArgs &a, float *lds, 
         srcA[j] = a.A + ra * a.lda + 4 * kc;
         srcB[j] = a.A + rb * a.lda + 4 * kc;
     }
-    int aoff[L::GG], boff[L::GG];  // float offsets of block 0's fragment per group (block x: + x XSTRIDE bytes)
-#pragma unroll
-    for (int g = 0; g < L::GG; ++g) {
-        aoff[g] = L::off(wm * 64, 0, g, lane);
-        boff[g] = L::off(wn * 64, 0, g, lane);
-    }
-    // this wave's quarter: no MFMAs when it lies wholly below the diagonal or past n
-    Quarter q{m0 + wm * 64, n0 + wn * 64, diag, diag && wn < wm};
-    const bool live = !q.below && q.qr < a.n && q.qc < a.n;
-#pragma unroll
-    for (int x = 0; x < NB; ++x)
-#pragma unroll
-        for (int y = 0; y < NB; ++y) c[x][y] = typename L::acc_t{};
+}
+
+// f(Flag<DIAG>, Flag<LIVE>) for the run-time (diag, live): the k-loops take both as template arguments
+template <bool B>
+struct Flag {
+    static constexpr bool value = B;
+};
+template <class F>
+__device__ __forceinline__ void diag_live(bool diag, bool live, F f) {
     if (diag) {
-        if (live) kloop<MF, BK, NST, true, true>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c);
-        else kloop<MF, BK, NST, true, false>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c);
+        if (live) f(Flag<true>{}, Flag<true>{});
+        else f(Flag<true>{}, Flag<false>{});
     } else {
-        if (live) kloop<MF, BK, NST, false, true>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c);
-        else kloop<MF, BK, NST, false, false>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c);
+        if (live) f(Flag<false>{}, Flag<true>{});
+        else f(Flag<false>{}, Flag<false>{});
     }
+}
+
+// The k range [kb, ke) of tile `tile` into c (zeroed here); returns this wave's Quarter.
+template <int NST>
+__device__ __forceinline__ Quarter tile_compute(const DenseArgs &a, float *lds, int64_t tile, int64_t kb, int64_t ke,
+                                                int wave, int lane, Acc &c) {
+    int64_t bi, bj;
+    tile_coords(tile, a.nt, bi, bj);
+    const int64_t m0 = bi * kTile, n0 = bj * kTile;
+    const float *srcA[St::PW], *srcB[St::PW];
+    tile_sources(a, m0, n0, wave, lane, srcA, srcB);
+    const int wm = wave >> 1, wn = wave & 1;
+    int aoff[L::GG], boff[L::GG];
+    frag_offsets(wm, wn, lane, aoff, boff);
+    // quarter_of's flags from the tile's and the wave's coordinates instead of the 64-bit row / column compare: with
+    // quarter_of here gram_dense_sk_kernel's k-loop is scheduled with more s_nop (fp32 n = 10000: +0.6 %,
+    // profiles/AB_LOG.md "Dense Gram folded")
+    const bool diag = bi == bj;
+    const Quarter q{m0 + wm * 64, n0 + wn * 64, diag && wm == wn, diag && wn < wm};
+#pragma unroll
+    for (int x = 0; x < L::NBLK; ++x)
+#pragma unroll
+        for (int y = 0; y < L::NBLK; ++y) c[x][y] = f32x16{};
+    diag_live(diag, q.live(a.n), [&](auto D, auto V) {
+        kloop<NST, decltype(D)::value, decltype(V)::value>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c);
+    });
     return q;
 }
 
@@ -357,13 +378,9 @@ __device__ __forceinline__ Quarter tile_compute(const DenseArgs &a, float *lds, 
 // registers) into c and returns true.  Hand-off: slab stores -> every wave vmcnt(0) -> barrier -> agent
 // release -> ticket fetch_add; the last arriver resets the ticket, then agent acquire -> barrier -> loads.
 // `flag` is LDS the ring no longer uses (every wave is past its k-loop).
-template <int MF, int BK, int NW = 4, typename SlabOf>
-__device__ __forceinline__ bool split_combine(const DenseArgs &a,
-                                              typename Layout<MF, BK>::acc_t (&c)[Layout<MF, BK>::NBLK]
-                                                                                 [Layout<MF, BK>::NBLK],
-                                              int32_t *ticket, int64_t pieces, int64_t me, SlabOf slab_of,
-                                              int32_t *flag, int wave, int lane) {
-    using L = Layout<MF, BK>;
+template <int NW = 4, typename SlabOf>
+__device__ __forceinline__ bool split_combine(const DenseArgs &a, Acc &c, int32_t *ticket, int64_t pieces, int64_t me,
+                                              SlabOf slab_of, int32_t *flag, int wave, int lane) {
     constexpr int64_t kSlab = NW * 16 * 64;  // float4 per piece: [NW waves][16 float4][64 lanes]
     f32x4v *mine = reinterpret_cast<f32x4v *>(a.slabs) + slab_of(me) * kSlab + wave * 16 * 64 + lane;
 #pragma unroll
@@ -395,25 +412,20 @@ __device__ __forceinline__ bool split_combine(const DenseArgs &a,
     return true;
 }
 
-template <int MF, int BK>
-__device__ __forceinline__ void tile_write(const DenseArgs &a,
-                                           const typename Layout<MF, BK>::acc_t (&c)[Layout<MF, BK>::NBLK]
-                                                                                    [Layout<MF, BK>::NBLK],
-                                           const Quarter &q, int wave, int lane) {
+// Writes the wave's quarter of a finished item.  UPPER = false: the wide kernels, which are never launched upper_only
+// (with the test compiled in, gram_planes_wide_kernel spills 38 VGPRs instead of 28).
+template <bool UPPER = true>
+__device__ __forceinline__ void tile_write(const DenseArgs &a, const Acc &c, const Quarter &q, int lane) {
     if (q.qr >= a.n || q.qc >= a.n) return;
-    if (a.upper_only) write_quarter<MF, BK>(a, c, q.qr, q.qc, false, true, lane);
-    else if (!q.below) write_quarter<MF, BK>(a, c, q.qr, q.qc, q.diag && (wave >> 1) == (wave & 1), false, lane);
+    if (UPPER && a.upper_only) write_quarter(a, c, q.qr, q.qc, false, true, lane);
+    else if (!q.below) write_quarter(a, c, q.qr, q.qc, q.diag, false, lane);
 }
 
-// One work item per workgroup: a whole tile, or a k-slice of one of the split tiles.
-template <int MF, int BK, int NST, int WPE>
-__global__ __launch_bounds__(256, WPE) void gram_dense_mfma_kernel(DenseArgs a) {
-    using L = Layout<MF, BK>;
-    using St = Stage<BK>;
-    constexpr int NB = L::NBLK;
-    __shared__ __attribute__((aligned(16))) float lds[NST * 2 * St::F];  // (one array: the DMA ring)
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+// The 128-tile kernels' work: one item per workgroup, a whole tile or a k-slice of one of the split tiles.
+// compute(tile, kb, ke, c) computes the k range [kb, ke) of the tile into c and returns the wave's Quarter;
+// `flag` is the ring's LDS (split_combine).
+template <class Compute>
+__device__ __forceinline__ void tile_item(const DenseArgs &a, int32_t *flag, int wave, int lane, Compute compute) {
     const int64_t w = blockIdx.x;
     int64_t tile, slice = 0, pieces = 1;
     if (w < a.n_whole) {
@@ -425,54 +437,70 @@ __global__ __launch_bounds__(256, WPE) void gram_dense_mfma_kernel(DenseArgs a) 
     }
     const int64_t kb = pieces > 1 ? slice * a.k_split : 0;
     const int64_t ke = pieces > 1 ? (kb + a.k_split < a.kpad ? kb + a.k_split : a.kpad) : a.kpad;
-    typename L::acc_t c[NB][NB];
-    const Quarter q = tile_compute<MF, BK, NST>(a, lds, tile, kb, ke, wave, lane, c);
+    Acc c;
+    const Quarter q = compute(tile, kb, ke, c);
     if (pieces > 1) {
         const int64_t u = tile - a.n_whole;
-        if (!split_combine<MF, BK>(a, c, a.tickets + u, pieces, slice, [&](int64_t s) { return u * pieces + s; },
-                                   reinterpret_cast<int32_t *>(lds), wave, lane))
+        if (!split_combine(a, c, a.tickets + u, pieces, slice, [&](int64_t s) { return u * pieces + s; }, flag, wave,
+                           lane))
             return;
     }
-    tile_write<MF, BK>(a, c, q, wave, lane);
+    tile_write(a, c, q, lane);
 }
 
-// Stream-K: slot (workgroup) s takes the k-tile units [s U, (s + 1) U) of the tiles laid end to end (tile t
-// = units [t KT, (t + 1) KT)), so every slot does the same MFMA work and the split tiles' hand-offs fall at
-// different times instead of in one burst at the end.  A tile wholly inside a slot is written directly; a
-// tile cut by slot boundaries has pieces in slots s0 .. s1, piece j's slab being slot (s0 + j)'s first
-// segment (j >= 1) -- slab 2 slot -- or, for j = 0, slot s0's last segment (slab 2 s0 + 1) unless the tile
+// Stream-K: slot (workgroup) s takes the k-tile units [s U, (s + 1) U) of the items laid end to end (item t
+// = units [t KT, (t + 1) KT)), so every slot does the same MFMA work and the split items' hand-offs fall at
+// different times instead of in one burst at the end.  An item wholly inside a slot is written directly; an
+// item cut by slot boundaries has pieces in slots s0 .. s1, piece j's slab being slot (s0 + j)'s first
+// segment (j >= 1) -- slab 2 slot -- or, for j = 0, slot s0's last segment (slab 2 s0 + 1) unless the item
 // starts exactly at s0's start (slab 2 s0).  Each slot has at most one first and one last segment, so the
-// slabs and the tickets (indexed by piece 0's slab) are private to one tile per launch.
-template <int MF, int BK, int NST, int WPE>
+// slabs and the tickets (indexed by piece 0's slab) are private to one item per launch.
+// The items are the 128-tiles (NW = 4 waves, base = 0, slot = the workgroup) or the wide kernels' items (NW = 8),
+// whose units start at `base` after the whole-item rounds (wide_schedule); compute as tile_item's; UPPER as
+// tile_write's (whether the kernel is ever launched upper_only).
+template <int NW, bool UPPER, class Compute>
+__device__ __forceinline__ void stream_k(const DenseArgs &a, int64_t slot, int64_t base, int32_t *flag, int wave,
+                                         int lane, Compute compute) {
+    const int64_t U = a.sk_units, KT = a.sk_kt;
+    const int64_t u0 = base + slot * U;
+    const int64_t u1 = u0 + U < a.sk_total ? u0 + U : a.sk_total;
+    for (int64_t u = u0; u < u1;) {
+        const int64_t item = u / KT, tb = item * KT, te = tb + KT;
+        const int64_t se = u1 < te ? u1 : te;
+        __syncthreads();  // (the previous segment's ring reads and hand-off flag are done)
+        Acc c;
+        const Quarter q = compute(item, (u - tb) * kBK, (se - tb) * kBK, c);
+        bool write = true;
+        if (u != tb || se != te) {
+            const int64_t s0 = (tb - base) / U, s1 = (te - 1 - base) / U;
+            const int64_t first = 2 * s0 + (tb - base == s0 * U ? 0 : 1);
+            write = split_combine<NW>(a, c, a.tickets + first, s1 - s0 + 1, slot - s0,
+                                      [&](int64_t j) { return j == 0 ? first : 2 * (s0 + j); }, flag, wave, lane);
+        }
+        if (write) tile_write<UPPER>(a, c, q, lane);
+        u = se;
+    }
+}
+
+template <int NST, int WPE>
+__global__ __launch_bounds__(256, WPE) void gram_dense_mfma_kernel(DenseArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[NST * 2 * St::F];  // (one array: the DMA ring)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    tile_item(a, reinterpret_cast<int32_t *>(lds), wave, lane, [&](int64_t tile, int64_t kb, int64_t ke, Acc &c) {
+        return tile_compute<NST>(a, lds, tile, kb, ke, wave, lane, c);
+    });
+}
+
+template <int NST, int WPE>
 __global__ __launch_bounds__(256, WPE) void gram_dense_sk_kernel(DenseArgs a) {
-    using L = Layout<MF, BK>;
-    using St = Stage<BK>;
-    constexpr int NB = L::NBLK;
     __shared__ __attribute__((aligned(16))) float lds[NST * 2 * St::F];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t U = a.sk_units, KT = a.sk_kt;
-    const int64_t u0 = (int64_t)blockIdx.x * U;
-    const int64_t u1 = u0 + U < a.sk_total ? u0 + U : a.sk_total;
-    for (int64_t u = u0; u < u1;) {
-        const int64_t tile = u / KT, tb = tile * KT, te = tb + KT;
-        const int64_t se = u1 < te ? u1 : te;
-        __syncthreads();  // (the previous segment's ring reads and hand-off flag are done)
-        typename L::acc_t c[NB][NB];
-        const Quarter q =
-            tile_compute<MF, BK, NST>(a, lds, tile, (u - tb) * BK, (se - tb) * BK, wave, lane, c);
-        bool write = true;
-        if (u != tb || se != te) {
-            const int64_t s0 = tb / U, s1 = (te - 1) / U;
-            const int64_t first = 2 * s0 + (tb == s0 * U ? 0 : 1);
-            write = split_combine<MF, BK>(
-                a, c, a.tickets + first, s1 - s0 + 1, blockIdx.x - s0,
-                [&](int64_t j) { return j == 0 ? first : 2 * (s0 + j); }, reinterpret_cast<int32_t *>(lds), wave,
-                lane);
-        }
-        if (write) tile_write<MF, BK>(a, c, q, wave, lane);
-        u = se;
-    }
+    stream_k<4, true>(a, blockIdx.x, 0, reinterpret_cast<int32_t *>(lds), wave, lane,
+                [&](int64_t tile, int64_t kb, int64_t ke, Acc &c) {
+                    return tile_compute<NST>(a, lds, tile, kb, ke, wave, lane, c);
+                });
 }
 
 // ------------------------------------------------------------ fp32 on the bf16 matrix cores
@@ -492,7 +520,7 @@ __global__ __launch_bounds__(256, WPE) void gram_dense_sk_kernel(DenseArgs a) {
 // two workgroups per CU): the split is done in registers after the fragment reads, so the bytes staged
 // per k are the fp32 kernel's.  (Staging three bf16 planes instead, 1.5x the bytes, measured slower:
 // profiles/AB_LOG.md "split Gram".)  A lane's operand of one bf16 MFMA is 8 consecutive k of its row --
-// the two 16-B chunks the fp32 kernel reads for fragment groups 0 and 1 (Layout<32, 16>::off).
+// the two 16-B chunks the fp32 kernel reads for fragment groups 0 and 1 (Layout::off).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // a plane fragment as 4 packed bf16 pairs
@@ -532,30 +560,30 @@ __device__ __forceinline__ void next_plane2(f32x4v &lo, f32x4v &hi, const u32x4 
     }
 }
 
+// Product s of one block from the planes a[p], b[q] of its fragments: s = 0 the leading a0 b0 into c0, s = 1 .. 5
+// the corrections (p, q) = (0,1) (1,0) (0,2) (1,1) (2,0) into c1
+__device__ __forceinline__ void plane_product(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 &c0, f32x16 &c1, int s) {
+    constexpr int PQ[6][2] = {{0, 0}, {0, 1}, {1, 0}, {0, 2}, {1, 1}, {2, 0}};
+    f32x16 &c = s == 0 ? c0 : c1;
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[PQ[s][0]]),
+                                                __builtin_bit_cast(bf16x8, b[PQ[s][1]]), c, 0, 0, 0);
+}
+
 // One k-tile of a wave's 2 x 2 blocks: fragments ra[x] (A block x), rb[y] (B block y) -> 6 products per
 // block.  Plane 0 of all four fragments first (16 conversions), so the four a0 b0 products start at once;
 // planes 1 and 2 (two pairs of one fragment per gap) and the next k-tile's DMA pieces (issue(0 .. 3)) go
 // between the MFMAs, each plane ready before the first product that reads it (sched_barrier fences).  Each
 // block's c1 still takes its five products in the order s = 1 .. 5, so the sums are bitwise unchanged.
 template <typename Issue>
-__device__ __forceinline__ void split_ktile(f32x4v (&ra)[2][2], f32x4v (&rb)[2][2], f32x16 (&c0)[2][2],
-                                            f32x16 (&c1)[2][2], Issue issue) {
+__device__ __forceinline__ void split_ktile(f32x4v (&ra)[2][2], f32x4v (&rb)[2][2], Acc &c0,
+                                            Acc &c1, Issue issue) {
     u32x4 a[2][3], b[2][3];
     plane0(ra[0][0], ra[0][1], a[0][0]);
     plane0(rb[0][0], rb[0][1], b[0][0]);
     plane0(ra[1][0], ra[1][1], a[1][0]);
     plane0(rb[1][0], rb[1][1], b[1][0]);
     __builtin_amdgcn_sched_barrier(0);
-    auto mf = [&](int x, int y, int s) {
-        if (s == 0) {
-            c0[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[x][0]),
-                                                             __builtin_bit_cast(bf16x8, b[y][0]), c0[x][y], 0, 0, 0);
-            return;
-        }
-        constexpr int P[6][2] = {{0, 0}, {0, 1}, {1, 0}, {0, 2}, {1, 1}, {2, 0}};
-        c1[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[x][P[s][0]]),
-                                                         __builtin_bit_cast(bf16x8, b[y][P[s][1]]), c1[x][y], 0, 0, 0);
-    };
+    auto mf = [&](int x, int y, int s) { plane_product(a[x], b[y], c0[x][y], c1[x][y], s); };
     auto fence = [] { __builtin_amdgcn_sched_barrier(0); };
     // (each line: the product, then the work that fits behind it; comments name what the product reads)
     mf(0, 0, 0); next_plane2<0>(ra[0][0], ra[0][1], a[0][0], a[0][1]); fence();  // A0 p1
@@ -584,93 +612,77 @@ __device__ __forceinline__ void split_ktile(f32x4v (&ra)[2][2], f32x4v (&rb)[2][
     mf(1, 1, 5);
 }
 
-// The k-loop of one tile over [kb, ke) with the split products.  The ring, the DMA pieces (issue: all of
-// k-tile t's) and the retire/publish step are kloop's; per k-tile a wave reads its 2 + 2 blocks' two chunks,
-// splits them and issues 4 blocks x 6 MFMAs.
-template <int NST, bool DIAG, bool LIVE>
-__device__ __forceinline__ void kloop_split(float *lds, const float *const *srcA, const float *const *srcB, int64_t kb,
-                                            int64_t ke, int wave, const int *aoff, const int *boff,
-                                            f32x16 (&c0)[2][2], f32x16 (&c1)[2][2]) {
-    using L = Layout<32, 16>;
-    using St = Stage<16>;
-    constexpr int G = DIAG ? St::PW : 2 * St::PW;  // DMA pieces per wave per k-tile
-    const int64_t nk = (ke - kb) / 16;
-    // k-tile t's pieces into stage t % NST.  Issued unconditionally, the k-tiles past the last re-load the last
-    // one into a stage nothing reads again (no branch in the MFMA region; every wait is the same count)
-    auto issue = [&](int64_t t) {
-        float *base = lds + (int)(t % NST) * 2 * St::F + wave * St::PW * 256;
-        const int64_t k0 = kb + (t < nk ? t : nk - 1) * 16;
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-            if (j < St::PW) dma16(srcA[j] + k0, base + j * 256);
-            else dma16(srcB[j - St::PW] + k0, base + St::F + (j - St::PW) * 256);
-        }
-    };
-    auto issue_part = [&](int64_t t, int q) {  // piece q of k-tile t's G (<= 4) pieces
-        if (q >= G) return;
-        float *base = lds + (int)(t % NST) * 2 * St::F + wave * St::PW * 256;
-        const int64_t k0 = kb + (t < nk ? t : nk - 1) * 16;
-        if (q < St::PW) dma16(srcA[q] + k0, base + q * 256);
-        else dma16(srcB[q - St::PW] + k0, base + St::F + (q - St::PW) * 256);
-    };
+// The ring k-loop of the bf16 kernels over nk k-tiles of G DMA pieces per wave: NST - 1 k-tiles issued ahead, one
+// barrier per k-tile (the retire/publish step is kloop's).  issue_part(t, q) issues piece q (< G) of k-tile t
+// into stage t % NST; it is called for t up to nk + NST - 2 and loads k-tile min(t, nk - 1): issued
+// unconditionally, the k-tiles past the last re-load the last one into a stage nothing reads again (no branch in
+// the MFMA region; every wait is the same count).  ktile(t, between) runs k-tile t's fragment reads and MFMAs and
+// calls between(0), between(1), ... in the gaps, which issue the pieces of k-tile t + NST - 1 (q >= G: nothing).
+// A dead wave (LIVE = false) only issues its pieces and joins the barriers.
+template <int NST, int G, bool LIVE, class IssuePart, class KTile>
+__device__ __forceinline__ void ring_kloop(int64_t nk, IssuePart issue_part, KTile ktile) {
     if (nk <= 0) return;
 #pragma unroll
-    for (int t = 0; t < NST - 1; ++t) issue(t);
+    for (int t = 0; t < NST - 1; ++t)
+#pragma unroll
+        for (int q = 0; q < G; ++q) issue_part(t, q);
     for (int64_t t = 0; t < nk; ++t) {
         wait_vm<(NST - 2) * G>();  // k-tile t landed (the NST - 2 younger ones may stay in flight), then published
         __builtin_amdgcn_s_barrier();  // (also: every wave is done with k-tile t - 1, whose stage refills now)
         asm volatile("" ::: "memory");
         if constexpr (!LIVE) {
-            issue(t + NST - 1);
+#pragma unroll
+            for (int q = 0; q < G; ++q) issue_part(t + NST - 1, q);
         } else {
-            const float *As = lds + (int)(t % NST) * 2 * St::F;
-            const float *Bs = DIAG ? As : As + St::F;
-            const char *pa = reinterpret_cast<const char *>(As), *pb = reinterpret_cast<const char *>(Bs);
-            f32x4v ra[2][2], rb[2][2];
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    ra[x][g] = *reinterpret_cast<const f32x4v *>(pa + aoff[g] * 4 + x * L::XSTRIDE);
-                    rb[x][g] = *reinterpret_cast<const f32x4v *>(pb + boff[g] * 4 + x * L::XSTRIDE);
-                }
-            split_ktile(ra, rb, c0, c1, [&](int q) { issue_part(t + NST - 1, q); });
+            ktile(t, [&](int q) { if (q < G) issue_part(t + NST - 1, q); });
         }
     }
 }
 
+// One k-tile from fp32 images: a wave reads its 2 + 2 blocks' two chunks (A image at As, B image at Bs), splits
+// them and issues 4 blocks x 6 MFMAs.
+template <typename Issue>
+__device__ __forceinline__ void split_ktile_lds(const float *As, const float *Bs, const int *aoff, const int *boff,
+                                                Acc &c0, Acc &c1, Issue issue) {
+    const char *pa = reinterpret_cast<const char *>(As), *pb = reinterpret_cast<const char *>(Bs);
+    f32x4v ra[2][2], rb[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            ra[x][g] = *reinterpret_cast<const f32x4v *>(pa + aoff[g] * 4 + x * L::XSTRIDE);
+            rb[x][g] = *reinterpret_cast<const f32x4v *>(pb + boff[g] * 4 + x * L::XSTRIDE);
+        }
+    split_ktile(ra, rb, c0, c1, issue);
+}
+
+// The k-loop of one tile over [kb, ke) with the split products: the fp32 path's stages and DMA pieces (kloop).
+template <int NST, bool DIAG, bool LIVE>
+__device__ __forceinline__ void kloop_split(float *lds, const float *const *srcA, const float *const *srcB, int64_t kb,
+                                            int64_t ke, int wave, const int *aoff, const int *boff, Acc &c0, Acc &c1) {
+    constexpr int G = DIAG ? St::PW : 2 * St::PW;  // DMA pieces per wave per k-tile (<= 4)
+    const int64_t nk = (ke - kb) / kBK;
+    ring_kloop<NST, G, LIVE>(
+        nk,
+        [&](int64_t t, int q) {
+            float *base = lds + (int)(t % NST) * 2 * St::F + wave * St::PW * 256;
+            const int64_t k0 = kb + (t < nk ? t : nk - 1) * kBK;
+            if (q < St::PW) dma16(srcA[q] + k0, base + q * 256);
+            else dma16(srcB[q - St::PW] + k0, base + St::F + (q - St::PW) * 256);
+        },
+        [&](int64_t t, auto between) {
+            const float *As = lds + (int)(t % NST) * 2 * St::F;
+            split_ktile_lds(As, DIAG ? As : As + St::F, aoff, boff, c0, c1, between);
+        });
+}
+
 constexpr int kSplitNST = 4;
 
-__device__ __forceinline__ Quarter tile_compute_split(const DenseArgs &a, float *lds, int64_t tile, int64_t kb,
-                                                      int64_t ke, int wave, int lane, f32x16 (&c)[2][2]) {
-    using L = Layout<32, 16>;
-    using St = Stage<16>;
-    const int wm = wave >> 1, wn = wave & 1;
-    int64_t bi, bj;
-    tile_coords(tile, a.nt, bi, bj);
-    const int64_t m0 = bi * kTile, n0 = bj * kTile;
-    const bool diag = bi == bj;
-    // the fp32 path's DMA sources (tile_compute)
-    const float *srcA[St::PW], *srcB[St::PW];
-#pragma unroll
-    for (int j = 0; j < St::PW; ++j) {
-        const int p = (wave * St::PW + j) * 64 + lane;
-        const int row = p / L::C, kc = (p % L::C) ^ L::swz(row);
-        int64_t ra = m0 + row, rb = n0 + row;
-        ra = ra < a.n ? ra : a.n - 1;
-        rb = rb < a.n ? rb : a.n - 1;
-        srcA[j] = a.A + ra * a.lda + 4 * kc;
-        srcB[j] = a.A + rb * a.lda + 4 * kc;
-    }
-    int aoff[2], boff[2];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        aoff[g] = L::off(wm * 64, 0, g, lane);
-        boff[g] = L::off(wn * 64, 0, g, lane);
-    }
-    Quarter q{m0 + wm * 64, n0 + wn * 64, diag, diag && wn < wm};
-    const bool live = !q.below && q.qr < a.n && q.qc < a.n;
-    f32x16 c0[2][2], c1[2][2];
+// The bf16 kernels' two sums: run(c0, c1) accumulates the leading products into c0 and the corrections into c1
+// (both zeroed here); c = c0 + c1.
+template <class Run>
+__device__ __forceinline__ void two_sums(Acc &c, Run run) {
+    Acc c0, c1;
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -678,72 +690,50 @@ __device__ __forceinline__ Quarter tile_compute_split(const DenseArgs &a, float 
             c0[x][y] = f32x16{};
             c1[x][y] = f32x16{};
         }
-    if (diag) {
-        if (live) kloop_split<kSplitNST, true, true>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c0, c1);
-        else kloop_split<kSplitNST, true, false>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c0, c1);
-    } else {
-        if (live) kloop_split<kSplitNST, false, true>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c0, c1);
-        else kloop_split<kSplitNST, false, false>(lds, srcA, srcB, kb, ke, wave, aoff, boff, c0, c1);
-    }
+    run(c0, c1);
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
         for (int y = 0; y < 2; ++y) c[x][y] = c0[x][y] + c1[x][y];
+}
+
+__device__ __forceinline__ Quarter tile_compute_split(const DenseArgs &a, float *lds, int64_t tile, int64_t kb,
+                                                      int64_t ke, int wave, int lane, Acc &c) {
+    int64_t bi, bj;
+    tile_coords(tile, a.nt, bi, bj);
+    const int64_t m0 = bi * kTile, n0 = bj * kTile;
+    const float *srcA[St::PW], *srcB[St::PW];
+    tile_sources(a, m0, n0, wave, lane, srcA, srcB);
+    int aoff[L::GG], boff[L::GG];
+    frag_offsets(wave >> 1, wave & 1, lane, aoff, boff);
+    const Quarter q = quarter_of(m0, n0, wave >> 1, wave & 1);
+    two_sums(c, [&](Acc &c0, Acc &c1) {
+        diag_live(bi == bj, q.live(a.n), [&](auto D, auto V) {
+            kloop_split<kSplitNST, decltype(D)::value, decltype(V)::value>(lds, srcA, srcB, kb, ke, wave, aoff, boff,
+                                                                           c0, c1);
+        });
+    });
     return q;
 }
 
 // the split path's kernels: the same work items as gram_dense_mfma_kernel / gram_dense_sk_kernel
 __global__ __launch_bounds__(256, 2) void gram_split_mfma_kernel(DenseArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[kSplitNST * 2 * Stage<16>::F];
+    __shared__ __attribute__((aligned(16))) float lds[kSplitNST * 2 * St::F];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t w = blockIdx.x;
-    int64_t tile, slice = 0, pieces = 1;
-    if (w < a.n_whole) {
-        tile = w;
-    } else {
-        tile = a.n_whole + (w - a.n_whole) / a.n_split;
-        slice = (w - a.n_whole) % a.n_split;
-        pieces = a.n_split;
-    }
-    const int64_t kb = pieces > 1 ? slice * a.k_split : 0;
-    const int64_t ke = pieces > 1 ? (kb + a.k_split < a.kpad ? kb + a.k_split : a.kpad) : a.kpad;
-    f32x16 c[2][2];
-    const Quarter q = tile_compute_split(a, lds, tile, kb, ke, wave, lane, c);
-    if (pieces > 1) {
-        const int64_t u = tile - a.n_whole;
-        if (!split_combine<32, 16>(a, c, a.tickets + u, pieces, slice, [&](int64_t s) { return u * pieces + s; },
-                                   reinterpret_cast<int32_t *>(lds), wave, lane))
-            return;
-    }
-    tile_write<32, 16>(a, c, q, wave, lane);
+    tile_item(a, reinterpret_cast<int32_t *>(lds), wave, lane, [&](int64_t tile, int64_t kb, int64_t ke, Acc &c) {
+        return tile_compute_split(a, lds, tile, kb, ke, wave, lane, c);
+    });
 }
 
 __global__ __launch_bounds__(256, 2) void gram_split_sk_kernel(DenseArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[kSplitNST * 2 * Stage<16>::F];
+    __shared__ __attribute__((aligned(16))) float lds[kSplitNST * 2 * St::F];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t U = a.sk_units, KT = a.sk_kt;
-    const int64_t u0 = (int64_t)blockIdx.x * U;
-    const int64_t u1 = u0 + U < a.sk_total ? u0 + U : a.sk_total;
-    for (int64_t u = u0; u < u1;) {
-        const int64_t tile = u / KT, tb = tile * KT, te = tb + KT;
-        const int64_t se = u1 < te ? u1 : te;
-        __syncthreads();  // (the previous segment's ring reads and hand-off flag are done)
-        f32x16 c[2][2];
-        const Quarter q = tile_compute_split(a, lds, tile, (u - tb) * 16, (se - tb) * 16, wave, lane, c);
-        bool write = true;
-        if (u != tb || se != te) {
-            const int64_t s0 = tb / U, s1 = (te - 1) / U;
-            const int64_t first = 2 * s0 + (tb == s0 * U ? 0 : 1);
-            write = split_combine<32, 16>(
-                a, c, a.tickets + first, s1 - s0 + 1, blockIdx.x - s0,
-                [&](int64_t j) { return j == 0 ? first : 2 * (s0 + j); }, reinterpret_cast<int32_t *>(lds), wave,
-                lane);
-        }
-        if (write) tile_write<32, 16>(a, c, q, wave, lane);
-        u = se;
-    }
+    stream_k<4, true>(a, blockIdx.x, 0, reinterpret_cast<int32_t *>(lds), wave, lane,
+                [&](int64_t tile, int64_t kb, int64_t ke, Acc &c) {
+                    return tile_compute_split(a, lds, tile, kb, ke, wave, lane, c);
+                });
 }
 
 // Wide workgroups for the split path (large n): 8 waves own a 256 x 128 item -- the row-block pair
@@ -776,50 +766,25 @@ __device__ __forceinline__ void item_coords(int64_t b, int64_t nt, int64_t &p, i
 
 template <int NST, bool LIVE>
 __device__ __forceinline__ void kloop_wide(float *lds, const float *const *src, const int *dst, int64_t kb, int64_t ke,
-                                           const int *aoff, const int *boff, f32x16 (&c0)[2][2],
-                                           f32x16 (&c1)[2][2]) {
-    using L = Layout<32, 16>;
+                                           const int *aoff, const int *boff, Acc &c0, Acc &c1) {
     constexpr int G = WideStage::PW;
-    static_assert(G == 3, "the DMA placement below is written for 3 pieces per wave");
-    const int64_t nk = (ke - kb) / 16;
-    auto issue_part = [&](int64_t t, int q) {
-        const int64_t k0 = kb + (t < nk ? t : nk - 1) * 16;
-        dma16(src[q] + k0, lds + (int)(t % NST) * WideStage::F + dst[q]);
-    };
-    if (nk <= 0) return;
-#pragma unroll
-    for (int t = 0; t < NST - 1; ++t)
-#pragma unroll
-        for (int q = 0; q < G; ++q) issue_part(t, q);
-    for (int64_t t = 0; t < nk; ++t) {
-        wait_vm<(NST - 2) * G>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if constexpr (!LIVE) {
-#pragma unroll
-            for (int q = 0; q < G; ++q) issue_part(t + NST - 1, q);
-        } else {
+    static_assert(G == 3, "item_compute_wide's pieces and split_ktile's four DMA gaps: 3 pieces per wave");
+    const int64_t nk = (ke - kb) / kBK;
+    ring_kloop<NST, G, LIVE>(
+        nk,
+        [&](int64_t t, int q) {
+            const int64_t k0 = kb + (t < nk ? t : nk - 1) * kBK;
+            dma16(src[q] + k0, lds + (int)(t % NST) * WideStage::F + dst[q]);
+        },
+        [&](int64_t t, auto between) {
             const float *As = lds + (int)(t % NST) * WideStage::F;
-            const char *pa = reinterpret_cast<const char *>(As);
-            const char *pb = reinterpret_cast<const char *>(As + WideStage::FA);
-            f32x4v ra[2][2], rb[2][2];
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    ra[x][g] = *reinterpret_cast<const f32x4v *>(pa + aoff[g] * 4 + x * L::XSTRIDE);
-                    rb[x][g] = *reinterpret_cast<const f32x4v *>(pb + boff[g] * 4 + x * L::XSTRIDE);
-                }
-            split_ktile(ra, rb, c0, c1, [&](int q) { if (q < G) issue_part(t + NST - 1, q); });
-        }
-    }
+            split_ktile_lds(As, As + WideStage::FA, aoff, boff, c0, c1, between);
+        });
 }
 
 template <int NST>
 __device__ __forceinline__ Quarter item_compute_wide(const DenseArgs &a, float *lds, int64_t item, int64_t kb,
-                                                     int64_t ke, int wave, int lane, f32x16 (&c)[2][2]) {
-    using L = Layout<32, 16>;
-    const int wm = wave >> 1, wn = wave & 1;
+                                                     int64_t ke, int wave, int lane, Acc &c) {
     int64_t p, j;
     item_coords(item, a.nt, p, j);
     const int64_t m0 = 2 * p * kTile, n0 = j * kTile;
@@ -838,34 +803,19 @@ __device__ __forceinline__ Quarter item_compute_wide(const DenseArgs &a, float *
         src[i] = a.A + r * a.lda + 4 * kc;
         dst[i] = isA ? P * 256 : WideStage::FA + (P - PA) * 256;
     }
-    int aoff[2], boff[2];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        aoff[g] = L::off(wm * 64, 0, g, lane);
-        boff[g] = L::off(wn * 64, 0, g, lane);
-    }
-    const int64_t R = m0 + wm * 64, Cc = n0 + wn * 64;
-    Quarter q{R, Cc, R == Cc, R > Cc};
-    const bool live = !q.below && R < a.n && Cc < a.n;
-    f32x16 c0[2][2], c1[2][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            c0[x][y] = f32x16{};
-            c1[x][y] = f32x16{};
-        }
-    if (live) kloop_wide<NST, true>(lds, src, dst, kb, ke, aoff, boff, c0, c1);
-    else kloop_wide<NST, false>(lds, src, dst, kb, ke, aoff, boff, c0, c1);
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) c[x][y] = c0[x][y] + c1[x][y];
+    const int wm = wave >> 1, wn = wave & 1;
+    int aoff[L::GG], boff[L::GG];
+    frag_offsets(wm, wn, lane, aoff, boff);
+    const Quarter q = quarter_of(m0, n0, wm, wn);
+    two_sums(c, [&](Acc &c0, Acc &c1) {  // (a diagonal item stages its B rows all the same: no DIAG arm)
+        if (q.live(a.n)) kloop_wide<NST, true>(lds, src, dst, kb, ke, aoff, boff, c0, c1);
+        else kloop_wide<NST, false>(lds, src, dst, kb, ke, aoff, boff, c0, c1);
+    });
     return q;
 }
 
 // The wide kernels' schedule.  Slot s of the grid G (one workgroup per CU) takes whole items in rounds -- round r's
-// item r G + s -- then an equal share of the k-tile units of the items left, stream-K (split items summed in piece
+// item r G + s -- then an equal share of the k-tile units of the items left (stream_k: split items summed in piece
 // order by the last piece, as gram_split_sk_kernel over the tiles).  With xcd_slots the slots are numbered
 // XCD-contiguously: workgroups are dealt round-robin over the 8 XCDs, so slot = (b mod 8) (G / 8) + b / 8 gives
 // the 32 CUs of one XCD 32 consecutive items of a round -- mostly one row pair against consecutive column blocks --
@@ -880,31 +830,11 @@ __device__ __forceinline__ void wide_schedule(const DenseArgs &a, int32_t *lds_s
     const int64_t KT = a.sk_kt;
     for (int64_t r = 0; r < a.dp_rounds; ++r) {
         __syncthreads();
-        f32x16 c[2][2];
-        const Quarter q = item_fn(r * G + slot, (int64_t)0, KT * 16, c);
-        if (!q.below && q.qr < a.n && q.qc < a.n) write_quarter<32, 16>(a, c, q.qr, q.qc, q.diag, false, lane);
+        Acc c;
+        const Quarter q = item_fn(r * G + slot, (int64_t)0, KT * kBK, c);
+        tile_write<false>(a, c, q, lane);
     }
-    const int64_t U = a.sk_units, base = a.dp_rounds * G * KT;
-    const int64_t u0 = base + slot * U;
-    const int64_t u1 = u0 + U < a.sk_total ? u0 + U : a.sk_total;
-    for (int64_t u = u0; u < u1;) {
-        const int64_t item = u / KT, tb = item * KT, te = tb + KT;
-        const int64_t se = u1 < te ? u1 : te;
-        __syncthreads();
-        f32x16 c[2][2];
-        const Quarter q = item_fn(item, (u - tb) * 16, (se - tb) * 16, c);
-        bool write = true;
-        if (u != tb || se != te) {
-            const int64_t s0 = (tb - base) / U, s1 = (te - 1 - base) / U;
-            const int64_t first = 2 * s0 + (tb - base == s0 * U ? 0 : 1);
-            write = split_combine<32, 16, 8>(
-                a, c, a.tickets + first, s1 - s0 + 1, slot - s0,
-                [&](int64_t j) { return j == 0 ? first : 2 * (s0 + j); }, lds_scratch, wave, lane);
-        }
-        if (write && !q.below && q.qr < a.n && q.qc < a.n)
-            write_quarter<32, 16>(a, c, q.qr, q.qc, q.diag, false, lane);
-        u = se;
-    }
+    stream_k<8, false>(a, slot, a.dp_rounds * G * KT, lds_scratch, wave, lane, item_fn);
 }
 
 template <int NST>
@@ -913,7 +843,7 @@ __global__ __launch_bounds__(512, 1) void gram_split_wide_kernel(DenseArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     wide_schedule(a, reinterpret_cast<int32_t *>(lds), wave, lane,
-                  [&](int64_t item, int64_t kb, int64_t ke, f32x16 (&c)[2][2]) {
+                  [&](int64_t item, int64_t kb, int64_t ke, Acc &c) {
                       return item_compute_wide<NST>(a, lds, item, kb, ke, wave, lane, c);
                   });
 }
@@ -987,7 +917,9 @@ __global__ __launch_bounds__(256) void densify_padded_planes_kernel(int64_t cap,
 struct PlaneStage {
     static constexpr int RA = 2 * kTile, RB = kTile;
     static constexpr int BA = RA * kPlaneBytes, BB = RB * kPlaneBytes, B = BA + BB;  // bytes
-    static constexpr int NP = B / 1024, G = (NP + 7) / 8;  // pieces per stage, per wave
+    static constexpr int WAVES = 8, NP = B / 1024, G = (NP + 7) / 8;  // pieces per stage, per wave
+    static constexpr int GD = G;                                       // (a diagonal item stages its B rows too)
+    static constexpr bool SIX = false;
 };
 static_assert(PlaneStage::B % 1024 == 0, "whole pieces");
 __device__ __forceinline__ uint32_t plane_lds_off(int row, int c) { return (uint32_t)(row * kPlaneBytes + 16 * (c ^ ((row >> 3) & 1))); }
@@ -1003,7 +935,7 @@ __device__ __forceinline__ void dma16b(const unsigned char *src, unsigned char *
 // ((row >> 3) & 1) = ((lane >> 3) & 1), so one base per operand and immediate offsets address all six)
 template <bool SIX = false, typename Issue>
 __device__ __forceinline__ void planes_ktile(const unsigned char *As, const unsigned char *Bs, uint32_t abase,
-                                             uint32_t bbase, f32x16 (&c0)[2][2], f32x16 (&c1)[2][2], Issue issue) {
+                                             uint32_t bbase, Acc &c0, Acc &c1, Issue issue) {
     u32x4 a[2][3], b[2][3];
 #pragma unroll
     for (int x = 0; x < 2; ++x)
@@ -1012,16 +944,7 @@ __device__ __forceinline__ void planes_ktile(const unsigned char *As, const unsi
             a[x][p] = *reinterpret_cast<const u32x4 *>(As + abase + 32 * kPlaneBytes * x + 32 * p);
             b[x][p] = *reinterpret_cast<const u32x4 *>(Bs + bbase + 32 * kPlaneBytes * x + 32 * p);
         }
-    auto mf = [&](int x, int y, int s) {
-        if (s == 0) {
-            c0[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[x][0]),
-                                                             __builtin_bit_cast(bf16x8, b[y][0]), c0[x][y], 0, 0, 0);
-            return;
-        }
-        constexpr int PQ[6][2] = {{0, 0}, {0, 1}, {1, 0}, {0, 2}, {1, 1}, {2, 0}};
-        c1[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[x][PQ[s][0]]),
-                                                         __builtin_bit_cast(bf16x8, b[y][PQ[s][1]]), c1[x][y], 0, 0, 0);
-    };
+    auto mf = [&](int x, int y, int s) { plane_product(a[x], b[y], c0[x][y], c1[x][y], s); };
     auto fence = [] { __builtin_amdgcn_sched_barrier(0); };
     mf(0, 0, 0); mf(0, 1, 0); mf(1, 0, 0); mf(1, 1, 0); fence();
     mf(0, 0, 1); issue(0); fence();
@@ -1046,53 +969,42 @@ __device__ __forceinline__ void planes_ktile(const unsigned char *As, const unsi
     mf(1, 1, 5);
 }
 
-template <int NST, bool LIVE>
+// The k-loop on the planes, for the stage geometry Stg (PlaneStage: the wide items; PlaneTileStage, below: the
+// 128-tiles, whose diagonal tiles stage the A image alone).
+template <class Stg, int NST, bool DIAG, bool LIVE>
 __device__ __forceinline__ void kloop_planes(unsigned char *lds, const unsigned char *const *src, const uint32_t *dst,
-                                             int64_t kb, int64_t ke, uint32_t abase, uint32_t bbase,
-                                             f32x16 (&c0)[2][2], f32x16 (&c1)[2][2]) {
-    constexpr int G = PlaneStage::G;
-    const int64_t nk = (ke - kb) / 16;
-    auto issue_part = [&](int64_t t, int q) {
-        const int64_t kt0 = kb / 16 + (t < nk ? t : nk - 1);
-        dma16b(src[q] + kPlaneBytes * kt0, lds + (int)(t % NST) * PlaneStage::B + dst[q]);
-    };
-    if (nk <= 0) return;
-#pragma unroll
-    for (int t = 0; t < NST - 1; ++t)
-#pragma unroll
-        for (int q = 0; q < G; ++q) issue_part(t, q);
-    for (int64_t t = 0; t < nk; ++t) {
-        wait_vm<(NST - 2) * G>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if constexpr (!LIVE) {
-#pragma unroll
-            for (int q = 0; q < G; ++q) issue_part(t + NST - 1, q);
-        } else {
-            const unsigned char *As = lds + (int)(t % NST) * PlaneStage::B;
-            planes_ktile(As, As + PlaneStage::BA, abase, bbase, c0, c1,
-                         [&](int q) { if (q < G) issue_part(t + NST - 1, q); });
-        }
-    }
+                                             int64_t kb, int64_t ke, uint32_t abase, uint32_t bbase, Acc &c0,
+                                             Acc &c1) {
+    constexpr int G = DIAG ? Stg::GD : Stg::G;
+    const int64_t nk = (ke - kb) / kBK;
+    ring_kloop<NST, G, LIVE>(
+        nk,
+        [&](int64_t t, int q) {
+            const int64_t kt0 = kb / kBK + (t < nk ? t : nk - 1);
+            dma16b(src[q] + kPlaneBytes * kt0, lds + (int)(t % NST) * Stg::B + dst[q]);
+        },
+        [&](int64_t t, auto between) {
+            const unsigned char *As = lds + (int)(t % NST) * Stg::B;
+            planes_ktile<Stg::SIX>(As, DIAG ? As : As + Stg::BA, abase, bbase, c0, c1, between);
+        });
 }
 
-template <int NST>
-__device__ __forceinline__ Quarter item_compute_planes(const DenseArgs &a, const unsigned char *P, int64_t ldp,
-                                                       unsigned char *lds, int64_t item, int64_t kb, int64_t ke,
-                                                       int wave, int lane, f32x16 (&c)[2][2]) {
-    const int wm = wave >> 1, wn = wave & 1;
-    int64_t p, j;
-    item_coords(item, a.nt, p, j);
-    const int64_t m0 = 2 * p * kTile, n0 = j * kTile;
-    const unsigned char *src[PlaneStage::G];
-    uint32_t dst[PlaneStage::G];
+// The k range [kb, ke) of the item whose A rows start at m0 and B rows at n0 (diag: B = A, one image staged) into
+// c; returns this wave's Quarter.  Piece i of wave w is piece w + WAVES i of the stage (past the last piece: the
+// wave's first again).
+template <class Stg, int NST>
+__device__ __forceinline__ Quarter planes_compute(const DenseArgs &a, const unsigned char *P, int64_t ldp,
+                                                  unsigned char *lds, int64_t m0, int64_t n0, bool diag, int64_t kb,
+                                                  int64_t ke, int wave, int lane, Acc &c) {
+    const unsigned char *src[Stg::G];
+    uint32_t dst[Stg::G];
 #pragma unroll
-    for (int i = 0; i < PlaneStage::G; ++i) {
-        int Pc = wave + 8 * i;
-        if (Pc >= PlaneStage::NP) Pc = wave;  // (the re-issued first piece)
+    for (int i = 0; i < Stg::G; ++i) {
+        int Pc = wave + Stg::WAVES * i;
+        if (Pc >= Stg::NP) Pc = wave;  // (the re-issued first piece)
         const uint32_t off = (uint32_t)Pc * 1024u + 16u * (uint32_t)lane;  // this lane's LDS bytes in the stage
-        const bool isA = off < (uint32_t)PlaneStage::BA;
-        const uint32_t o = isA ? off : off - PlaneStage::BA;
+        const bool isA = off < (uint32_t)Stg::BA;
+        const uint32_t o = isA ? off : off - Stg::BA;
         const int R = (int)(o / kPlaneBytes), jj = (int)((o % kPlaneBytes) / 16);
         const int cc = jj ^ ((R >> 3) & 1);  // the global chunk that lands here
         int64_t r = (isA ? m0 : n0) + R;
@@ -1100,25 +1012,16 @@ __device__ __forceinline__ Quarter item_compute_planes(const DenseArgs &a, const
         src[i] = P + r * ldp + 16 * cc;
         dst[i] = off;
     }
+    const int wm = wave >> 1, wn = wave & 1;
     const uint32_t abase = plane_lds_off(wm * 64 + (lane & 31), lane >> 5);
     const uint32_t bbase = plane_lds_off(wn * 64 + (lane & 31), lane >> 5);
-    const int64_t R = m0 + wm * 64, Cc = n0 + wn * 64;
-    Quarter q{R, Cc, R == Cc, R > Cc};
-    const bool live = !q.below && R < a.n && Cc < a.n;
-    f32x16 c0[2][2], c1[2][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            c0[x][y] = f32x16{};
-            c1[x][y] = f32x16{};
-        }
-    if (live) kloop_planes<NST, true>(lds, src, dst, kb, ke, abase, bbase, c0, c1);
-    else kloop_planes<NST, false>(lds, src, dst, kb, ke, abase, bbase, c0, c1);
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) c[x][y] = c0[x][y] + c1[x][y];
+    const Quarter q = quarter_of(m0, n0, wm, wn);
+    two_sums(c, [&](Acc &c0, Acc &c1) {
+        diag_live(diag, q.live(a.n), [&](auto D, auto V) {
+            kloop_planes<Stg, NST, decltype(D)::value, decltype(V)::value>(lds, src, dst, kb, ke, abase, bbase, c0,
+                                                                           c1);
+        });
+    });
     return q;
 }
 
@@ -1128,8 +1031,11 @@ __global__ __launch_bounds__(512, 1) void gram_planes_wide_kernel(DenseArgs a, c
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     wide_schedule(a, reinterpret_cast<int32_t *>(lds), wave, lane,
-                  [&](int64_t item, int64_t kb, int64_t ke, f32x16 (&c)[2][2]) {
-                      return item_compute_planes<NST>(a, P, ldp, lds, item, kb, ke, wave, lane, c);
+                  [&](int64_t item, int64_t kb, int64_t ke, Acc &c) {
+                      int64_t p, j;
+                      item_coords(item, a.nt, p, j);
+                      return planes_compute<PlaneStage, NST>(a, P, ldp, lds, 2 * p * kTile, j * kTile, false, kb, ke,
+                                                             wave, lane, c);
                   });
 }
 
@@ -1140,114 +1046,23 @@ __global__ __launch_bounds__(512, 1) void gram_planes_wide_kernel(DenseArgs a, c
 // and MFMAs of planes_ktile.  Same products in the same order as the in-register kernel: the same K bits.
 struct PlaneTileStage {
     static constexpr int BA = kTile * kPlaneBytes, B = 2 * BA;  // bytes: the A image, then the B image
-    static constexpr int G = B / 1024 / 4, GD = BA / 1024 / 4;  // pieces per wave and k-tile (off / on the diagonal)
+    static constexpr int WAVES = 4, NP = B / 1024;
+    static constexpr int G = NP / 4, GD = BA / 1024 / 4;  // pieces per wave and k-tile (off / on the diagonal)
+    static constexpr bool SIX = true;                     // (planes_ktile places the sixth piece)
 };
 static_assert(PlaneTileStage::BA % 4096 == 0 && PlaneTileStage::G == 6, "whole pieces, six per wave");
 constexpr int kPlaneTileNST = 3;
-
-template <int NST, bool DIAG, bool LIVE>
-__device__ __forceinline__ void kloop_planes_tile(unsigned char *lds, const unsigned char *const *src,
-                                                  const uint32_t *dst, int64_t kb, int64_t ke, uint32_t abase,
-                                                  uint32_t bbase, f32x16 (&c0)[2][2], f32x16 (&c1)[2][2]) {
-    constexpr int G = DIAG ? PlaneTileStage::GD : PlaneTileStage::G;
-    const int64_t nk = (ke - kb) / 16;
-    auto issue_part = [&](int64_t t, int q) {
-        const int64_t kt0 = kb / 16 + (t < nk ? t : nk - 1);
-        dma16b(src[q] + kPlaneBytes * kt0, lds + (int)(t % NST) * PlaneTileStage::B + dst[q]);
-    };
-    if (nk <= 0) return;
-#pragma unroll
-    for (int t = 0; t < NST - 1; ++t)
-#pragma unroll
-        for (int q = 0; q < G; ++q) issue_part(t, q);
-    for (int64_t t = 0; t < nk; ++t) {
-        wait_vm<(NST - 2) * G>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if constexpr (!LIVE) {
-#pragma unroll
-            for (int q = 0; q < G; ++q) issue_part(t + NST - 1, q);
-        } else {
-            const unsigned char *As = lds + (int)(t % NST) * PlaneTileStage::B;
-            const unsigned char *Bs = DIAG ? As : As + PlaneTileStage::BA;
-            planes_ktile<true>(As, Bs, abase, bbase, c0, c1, [&](int q) { if (q < G) issue_part(t + NST - 1, q); });
-        }
-    }
-}
-
-__device__ __forceinline__ Quarter tile_compute_planes(const DenseArgs &a, const unsigned char *P, int64_t ldp,
-                                                       unsigned char *lds, int64_t tile, int64_t kb, int64_t ke,
-                                                       int wave, int lane, f32x16 (&c)[2][2]) {
-    const int wm = wave >> 1, wn = wave & 1;
-    int64_t bi, bj;
-    tile_coords(tile, a.nt, bi, bj);
-    const int64_t m0 = bi * kTile, n0 = bj * kTile;
-    const bool diag = bi == bj;
-    const unsigned char *src[PlaneTileStage::G];
-    uint32_t dst[PlaneTileStage::G];
-#pragma unroll
-    for (int i = 0; i < PlaneTileStage::G; ++i) {
-        const uint32_t off = (uint32_t)(wave + 4 * i) * 1024u + 16u * (uint32_t)lane;  // this lane's stage bytes
-        const bool isA = off < (uint32_t)PlaneTileStage::BA;
-        const uint32_t o = isA ? off : off - PlaneTileStage::BA;
-        const int R = (int)(o / kPlaneBytes), jj = (int)((o % kPlaneBytes) / 16);
-        const int cc = jj ^ ((R >> 3) & 1);  // the global chunk that lands here
-        int64_t r = (isA ? m0 : n0) + R;
-        r = r < a.n ? r : a.n - 1;
-        src[i] = P + r * ldp + 16 * cc;
-        dst[i] = off;
-    }
-    const uint32_t abase = plane_lds_off(wm * 64 + (lane & 31), lane >> 5);
-    const uint32_t bbase = plane_lds_off(wn * 64 + (lane & 31), lane >> 5);
-    Quarter q{m0 + wm * 64, n0 + wn * 64, diag, diag && wn < wm};
-    const bool live = !q.below && q.qr < a.n && q.qc < a.n;
-    f32x16 c0[2][2], c1[2][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            c0[x][y] = f32x16{};
-            c1[x][y] = f32x16{};
-        }
-    constexpr int NST = kPlaneTileNST;
-    if (diag) {
-        if (live) kloop_planes_tile<NST, true, true>(lds, src, dst, kb, ke, abase, bbase, c0, c1);
-        else kloop_planes_tile<NST, true, false>(lds, src, dst, kb, ke, abase, bbase, c0, c1);
-    } else {
-        if (live) kloop_planes_tile<NST, false, true>(lds, src, dst, kb, ke, abase, bbase, c0, c1);
-        else kloop_planes_tile<NST, false, false>(lds, src, dst, kb, ke, abase, bbase, c0, c1);
-    }
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) c[x][y] = c0[x][y] + c1[x][y];
-    return q;
-}
 
 __global__ __launch_bounds__(256, 2) void gram_planes_tile_kernel(DenseArgs a, const unsigned char *P, int64_t ldp) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[kPlaneTileNST * PlaneTileStage::B];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t w = blockIdx.x;
-    int64_t tile, slice = 0, pieces = 1;
-    if (w < a.n_whole) {
-        tile = w;
-    } else {
-        tile = a.n_whole + (w - a.n_whole) / a.n_split;
-        slice = (w - a.n_whole) % a.n_split;
-        pieces = a.n_split;
-    }
-    const int64_t kb = pieces > 1 ? slice * a.k_split : 0;
-    const int64_t ke = pieces > 1 ? (kb + a.k_split < a.kpad ? kb + a.k_split : a.kpad) : a.kpad;
-    f32x16 c[2][2];
-    const Quarter q = tile_compute_planes(a, P, ldp, lds, tile, kb, ke, wave, lane, c);
-    if (pieces > 1) {
-        const int64_t u = tile - a.n_whole;
-        if (!split_combine<32, 16>(a, c, a.tickets + u, pieces, slice, [&](int64_t s) { return u * pieces + s; },
-                                   reinterpret_cast<int32_t *>(lds), wave, lane))
-            return;
-    }
-    tile_write<32, 16>(a, c, q, wave, lane);
+    tile_item(a, reinterpret_cast<int32_t *>(lds), wave, lane, [&](int64_t tile, int64_t kb, int64_t ke, Acc &c) {
+        int64_t bi, bj;
+        tile_coords(tile, a.nt, bi, bj);
+        return planes_compute<PlaneTileStage, kPlaneTileNST>(a, P, ldp, lds, bi * kTile, bj * kTile, bi == bj, kb, ke,
+                                                             wave, lane, c);
+    });
 }
 
 constexpr int kCUs = 256;
@@ -1267,18 +1082,20 @@ struct DensePlan {
     int64_t nt, tiles, n_whole, k_split, kpad;
     int32_t n_split;
     size_t ws_bytes;  // tickets + slabs
+    void whole_tiles_only() {  // (no workspace for slabs)
+        n_split = 1;
+        n_whole = tiles;
+        ws_bytes = 0;
+    }
 };
 
 // Work plan: whole tiles, and split pieces where whole tiles would leave CUs idle -- every tile split
 // when the tiles alone do not fill the GPU (small n), else the last `tail` tiles.
-// A/B knobs (read once): GRF_DENSE_SPLIT (pieces per split tile), GRF_DENSE_TAIL (split tiles at the end)
-DensePlan dense_plan(int64_t n, int64_t k_dim, int bk) {
+DensePlan dense_plan(int64_t n, int64_t k_dim) {
     DensePlan p{};
     p.nt = cdiv<int64_t>(n, kTile);
     p.tiles = p.nt * (p.nt + 1) / 2;
-    p.kpad = cdiv<int64_t>(k_dim, bk) * bk;
-    static const int env_split = env_int("GRF_DENSE_SPLIT", -1);
-    static const int env_tail = env_int("GRF_DENSE_TAIL", -1);
+    p.kpad = cdiv<int64_t>(k_dim, kBK) * kBK;
     constexpr int64_t slots = 2 * kCUs;  // workgroups resident at once (2 per CU: 64 KiB of LDS ring each)
     int64_t split = 1, tail = 0;
     if (p.tiles < slots) {  // small n: every tile split, ~2 pieces per CU slot
@@ -1290,15 +1107,13 @@ DensePlan dense_plan(int64_t n, int64_t k_dim, int bk) {
         split = 3;
         tail = std::min<int64_t>(p.tiles, slots + p.tiles % slots);
     }
-    if (env_split >= 1) split = env_split;
-    if (env_tail >= 0) tail = std::min<int64_t>(env_tail, p.tiles);
     tail = std::min<int64_t>(tail, kMaxSplitTiles);
-    const int64_t ktiles = p.kpad / bk;
+    const int64_t ktiles = p.kpad / kBK;
     split = std::max<int64_t>(1, std::min<int64_t>(split, ktiles));
     if (split == 1) tail = 0;
     p.n_split = (int32_t)split;
     p.n_whole = p.tiles - tail;
-    p.k_split = cdiv<int64_t>(ktiles, split) * bk;
+    p.k_split = cdiv<int64_t>(ktiles, split) * kBK;
     if (tail > 0) p.n_split = (int32_t)cdiv<int64_t>(p.kpad, p.k_split);  // (no empty piece)
     if (p.n_split <= 1) {
         p.n_split = 1;
@@ -1309,17 +1124,17 @@ DensePlan dense_plan(int64_t n, int64_t k_dim, int bk) {
     return p;
 }
 
-// Stream-K plan (GRF_DENSE_SK=1): slots = 2 workgroups per CU, U k-tile units each.
+// Stream-K plan: slots = 2 workgroups per CU, U k-tile units each.
 struct SkPlan {
     int64_t kt, total, units, grid;
     size_t ws_bytes;
     int64_t dp_rounds;  // (wide plan) whole-item rounds before the stream-K units
     int32_t xcd_slots;  // (wide plan) XCD-contiguous slot numbering
 };
-SkPlan sk_plan(int64_t n, int64_t k_dim, int bk) {
+SkPlan sk_plan(int64_t n, int64_t k_dim) {
     SkPlan p{};
     const int64_t nt = cdiv<int64_t>(n, kTile);
-    p.kt = cdiv<int64_t>(k_dim, bk);
+    p.kt = cdiv<int64_t>(k_dim, kBK);
     p.total = nt * (nt + 1) / 2 * p.kt;
     const int64_t slots = std::min<int64_t>(2 * kCUs, std::max<int64_t>(p.total, 1));
     p.units = std::max<int64_t>(1, cdiv<int64_t>(p.total, slots));
@@ -1336,7 +1151,7 @@ SkPlan sk_plan_wide(int64_t n, int64_t k_dim) {
     SkPlan p{};
     const int64_t nt = cdiv<int64_t>(n, kTile), np = (nt + 1) / 2;
     const int64_t items = np * (nt + 1) - np * np;
-    p.kt = cdiv<int64_t>(k_dim, 16);
+    p.kt = cdiv<int64_t>(k_dim, kBK);
     p.total = items * p.kt;
     const bool xcd = env_int("GRF_DENSE_XCD", 1) != 0;
     if (xcd && items >= 2 * kCUs) {
@@ -1355,84 +1170,107 @@ SkPlan sk_plan_wide(int64_t n, int64_t k_dim) {
     return p;
 }
 
-}  // namespace
+// The wide workgroups (256 x 128 items) from 64 tile rows on (n > 8064): C2 (n = 10 000) 5.60 -> 5.12 ms,
+// n = 16384 24.5 -> 22.7; equal at n = 6144, slower at C3 (0.148 -> 0.164: 132 items on 256 CUs, every one
+// cut) -- profiles/r05_split_gram_ab.txt.  GRF_DENSE_WIDE (read per call, for A/B and tests): 0 never,
+// 1 always, unset / -1 by that rule.
+bool wide_items(int64_t nt) {
+    const int wide_env = env_int("GRF_DENSE_WIDE", -1);
+    return wide_env == 1 || (wide_env != 0 && nt >= 64);
+}
+
+// The check on K every Gram entry point makes (`entry` names it in the message) and the fields every launch sets
+// (a: zero-initialised by the caller).
+int32_t dense_args(const char *entry, int64_t n, int64_t k_dim, float *K, int64_t ldk, bool upper_only, DenseArgs &a) {
+    GRF_REQUIRE(upper_only || (ldk % 4 == 0 && ((uintptr_t)K & 15) == 0), GRF_EINVAL,
+                "%s: ldk must be a multiple of 4 and K 16-byte aligned", entry);
+    a.K = K;
+    a.n = n;
+    a.nt = cdiv<int64_t>(n, kTile);
+    a.ldk = ldk;
+    a.kpad = cdiv<int64_t>(k_dim, kBK) * kBK;
+    a.upper_only = upper_only ? 1 : 0;
+    return GRF_OK;
+}
+
+// ... and those on an fp32 operand A
+int32_t dense_args_fp32(const char *entry, int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K,
+                        int64_t ldk, bool upper_only, DenseArgs &a) {
+    GRF_REQUIRE(n >= 0 && k_dim >= 0 && A && K && ldk >= n && lda >= k_dim, GRF_EINVAL, "%s: bad arguments", entry);
+    GRF_REQUIRE(lda % 16 == 0 && ((uintptr_t)A & 15) == 0, GRF_EINVAL,
+                "%s: lda must be a multiple of 16 and A 16-byte aligned", entry);
+    const int32_t rc = dense_args(entry, n, k_dim, K, ldk, upper_only, a);
+    a.A = A;
+    a.lda = lda;
+    return rc;
+}
+
+// the workspace: the ticket block, then the slabs
+void set_workspace(DenseArgs &a, void *workspace) {
+    a.tickets = reinterpret_cast<int32_t *>(workspace);
+    a.slabs = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + kTicketBytes);
+}
+
+// the tile plan's fields of a (the 128-tile kernels' tile_item); returns the grid, one workgroup per work item
+int64_t apply_plan(DenseArgs &a, const DensePlan &p, void *workspace) {
+    const int64_t split_tiles = p.tiles - p.n_whole;
+    if (split_tiles > 0) set_workspace(a, workspace);
+    a.n_whole = p.n_whole;
+    a.k_split = p.k_split;
+    a.n_split = p.n_split;
+    return p.n_whole + split_tiles * p.n_split;
+}
+
+// a stream-K plan's fields of a (stream_k, wide_schedule); the grid is q.grid
+void apply_plan(DenseArgs &a, const SkPlan &q, void *workspace) {
+    set_workspace(a, workspace);
+    a.sk_units = q.units;
+    a.sk_kt = q.kt;
+    a.sk_total = q.total;
+    a.dp_rounds = q.dp_rounds;
+    a.xcd_slots = q.xcd_slots;
+}
 
 size_t dense_gram_workspace_bytes(int64_t n, int64_t k_dim) {
     if (n <= 0) return 16;
-    const DensePlan p = dense_plan(n, k_dim, 16);
-    return std::max<size_t>(16, std::max(p.ws_bytes, sk_plan(n, k_dim, 16).ws_bytes));
+    return std::max<size_t>(16, std::max(dense_plan(n, k_dim).ws_bytes, sk_plan(n, k_dim).ws_bytes));
 }
 
+// The MFMA Gram: tiles on and above the diagonal written to both triangles (upper_only: the tiles' K[row][col]
+// only, the seed of the hub-column split's sparse tiles)
 int32_t dense_gram(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk, void *workspace,
                    size_t workspace_bytes, bool upper_only, grf_stream_t stream) {
-    GRF_REQUIRE(n >= 0 && k_dim >= 0 && A && K && ldk >= n && lda >= k_dim, GRF_EINVAL,
-                "grf_gram_dense: bad arguments");
-    GRF_REQUIRE(lda % 16 == 0 && ((uintptr_t)A & 15) == 0, GRF_EINVAL,
-                "grf_gram_dense: lda must be a multiple of 16 and A 16-byte aligned");
-    GRF_REQUIRE(upper_only || (ldk % 4 == 0 && ((uintptr_t)K & 15) == 0), GRF_EINVAL,
-                "grf_gram_dense: ldk must be a multiple of 4 and K 16-byte aligned");
-    if (n == 0) return GRF_OK;
-    constexpr int BK = 16;
-    DensePlan p = dense_plan(n, k_dim, BK);
-    GRF_REQUIRE(p.kpad <= lda, GRF_EINVAL, "grf_gram_dense: lda must cover k_dim rounded up to %d", BK);
     DenseArgs a{};
-    a.A = A;
-    a.K = K;
-    a.n = n;
-    a.nt = p.nt;
-    a.lda = lda;
-    a.ldk = ldk;
-    a.kpad = p.kpad;
-    a.upper_only = upper_only ? 1 : 0;
+    const int32_t rc = dense_args_fp32("grf_gram_dense", n, k_dim, A, lda, K, ldk, upper_only, a);
+    if (rc != GRF_OK || n == 0) return rc;
+    DensePlan p = dense_plan(n, k_dim);
+    GRF_REQUIRE(p.kpad <= lda, GRF_EINVAL, "grf_gram_dense: lda must cover k_dim rounded up to %d", kBK);
     hipStream_t st = S(stream);
     // stream-K when the tiles fill at least half the slots (every slot then takes >= half a tile of k, so a
     // split tile has <= 3 pieces): n = 4096 0.68 -> 0.78, C2 0.83 -> 0.86 of the MFMA peak; at C3 (253 tiles)
-    // even, below it the per-tile splits win (profiles/r04_dense_ab.txt).  GRF_DENSE_SK: 0 never, 1 always.
-    static const int sk_env = env_int("GRF_DENSE_SK", -1);
-    const bool sk = sk_env == 1 || (sk_env != 0 && p.tiles >= kCUs);
-    if (sk) {
-        const SkPlan q = sk_plan(n, k_dim, BK);
+    // even, below it the per-tile splits win (profiles/r04_dense_ab.txt).
+    if (p.tiles >= kCUs) {
+        const SkPlan q = sk_plan(n, k_dim);
         if (workspace && workspace_bytes >= q.ws_bytes && ((uintptr_t)workspace & 255) == 0) {
             GRF_REQUIRE_GRID(q.grid, 256, "gram_dense_sk_kernel");
-            a.tickets = reinterpret_cast<int32_t *>(workspace);
-            a.slabs = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + kTicketBytes);
-            a.sk_units = q.units;
-            a.sk_kt = q.kt;
-            a.sk_total = q.total;
-            gram_dense_sk_kernel<32, BK, 4, 2><<<(unsigned)q.grid, 256, 0, st>>>(a);
+            apply_plan(a, q, workspace);
+            gram_dense_sk_kernel<4, 2><<<(unsigned)q.grid, 256, 0, st>>>(a);
             GRF_CHECK_LAUNCH("gram_dense_sk_kernel");
             return GRF_OK;
         }
     }
-    if (p.ws_bytes > 0 && (!workspace || workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 255))) {
-        // no (or too small) workspace: whole tiles only
-        p.n_split = 1;
-        p.n_whole = p.tiles;
-        p.ws_bytes = 0;
-    }
-    const int64_t split_tiles = p.tiles - p.n_whole;
-    const int64_t items = p.n_whole + split_tiles * p.n_split;
+    if (p.ws_bytes > 0 && (!workspace || workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 255)))
+        p.whole_tiles_only();  // no (or too small) workspace
+    const int64_t items = apply_plan(a, p, workspace);
     GRF_REQUIRE_GRID(items, 256, "gram_dense_mfma_kernel");
-    a.tickets = split_tiles > 0 ? reinterpret_cast<int32_t *>(workspace) : nullptr;
-    a.slabs = split_tiles > 0 ? reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + kTicketBytes) : nullptr;
-    a.n_whole = p.n_whole;
-    a.k_split = p.k_split;
-    a.n_split = p.n_split;
     // the hub panel (upper_only, k of a few k-tiles): each tile is a short k-loop then a 64 KB write, so a
     // third workgroup per CU (3-stage ring, 48 KB) overlaps one tile's stores with the others' MFMAs: Enron's
     // panel 1.67 -> 1.49 ms, step 7.84-7.87 -> 7.62-7.71 ms (profiles/r04_hub_ring_ab.txt).
-    // GRF_DENSE_HUB_NST: 3 (default) or 4 (the ring of the other launches).
-    static const int hub_nst = env_int("GRF_DENSE_HUB_NST", 3);
-    if (upper_only && split_tiles == 0 && hub_nst == 3) {
-        gram_dense_mfma_kernel<32, BK, 3, 3><<<(unsigned)items, 256, 0, st>>>(a);
-        GRF_CHECK_LAUNCH("gram_dense_mfma_kernel");
-        return GRF_OK;
-    }
-    gram_dense_mfma_kernel<32, BK, 4, 2><<<(unsigned)items, 256, 0, st>>>(a);
+    if (upper_only && p.n_whole == p.tiles) gram_dense_mfma_kernel<3, 3><<<(unsigned)items, 256, 0, st>>>(a);
+    else gram_dense_mfma_kernel<4, 2><<<(unsigned)items, 256, 0, st>>>(a);
     GRF_CHECK_LAUNCH("gram_dense_mfma_kernel");
     return GRF_OK;
 }
-
 
 // The split path: the fp32 path's workspace (tickets and slabs; the ticket block must be zero on first use)
 size_t dense_gram_split_workspace_bytes(int64_t n, int64_t k_dim) {
@@ -1440,90 +1278,92 @@ size_t dense_gram_split_workspace_bytes(int64_t n, int64_t k_dim) {
     return n <= 0 ? base : std::max(base, sk_plan_wide(n, k_dim).ws_bytes);
 }
 
+// The same K on the bf16 matrix cores: A split exactly into three bf16 planes, six products per term.
 // workspace NULL (the hub panel's upper_only call): whole tiles only, as dense_gram without one
 int32_t dense_gram_split(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
                          void *workspace, size_t workspace_bytes, bool upper_only, grf_stream_t stream) {
-    GRF_REQUIRE(n >= 0 && k_dim >= 0 && A && K && ldk >= n && lda >= k_dim, GRF_EINVAL,
-                "grf_gram_dense_split: bad arguments");
-    GRF_REQUIRE(lda % 16 == 0 && ((uintptr_t)A & 15) == 0, GRF_EINVAL,
-                "grf_gram_dense_split: lda must be a multiple of 16 and A 16-byte aligned");
-    GRF_REQUIRE(upper_only || (ldk % 4 == 0 && ((uintptr_t)K & 15) == 0), GRF_EINVAL,
-                "grf_gram_dense_split: ldk must be a multiple of 4 and K 16-byte aligned");
-    if (n == 0) return GRF_OK;
+    DenseArgs a{};
+    const int32_t rc = dense_args_fp32("grf_gram_dense_split", n, k_dim, A, lda, K, ldk, upper_only, a);
+    if (rc != GRF_OK || n == 0) return rc;
     GRF_REQUIRE(!workspace || (((uintptr_t)workspace & 255) == 0 &&
                                workspace_bytes >= dense_gram_split_workspace_bytes(n, k_dim)),
                 GRF_EINVAL, "grf_gram_dense_split: workspace too small or not 256-byte aligned");
-    constexpr int BK = 16;
-    DensePlan p = dense_plan(n, k_dim, BK);
-    GRF_REQUIRE(p.kpad <= lda, GRF_EINVAL, "grf_gram_dense_split: lda must cover k_dim rounded up to %d", BK);
+    DensePlan p = dense_plan(n, k_dim);
+    GRF_REQUIRE(p.kpad <= lda, GRF_EINVAL, "grf_gram_dense_split: lda must cover k_dim rounded up to %d", kBK);
     hipStream_t st = S(stream);
-    DenseArgs a{};
-    a.A = A;
-    a.K = K;
-    a.n = n;
-    a.nt = p.nt;
-    a.lda = lda;
-    a.ldk = ldk;
-    a.kpad = p.kpad;
-    a.upper_only = upper_only ? 1 : 0;
-    // the wide workgroups (256 x 128 items) from 64 tile rows on (n > 8064): C2 (n = 10 000) 5.60 -> 5.12 ms,
-    // n = 16384 24.5 -> 22.7; equal at n = 6144, slower at C3 (0.148 -> 0.164: 132 items on 256 CUs, every one
-    // cut) -- profiles/r05_split_gram_ab.txt.  GRF_DENSE_WIDE (read per call, for A/B and tests): 0 never,
-    // 1 always, unset / -1 by that rule.
-    const int wide_env = env_int("GRF_DENSE_WIDE", -1);
-    const bool wide = wide_env == 1 || (wide_env != 0 && p.nt >= 64);
-    if (wide && workspace && !upper_only && p.kpad > 0) {
+    if (wide_items(p.nt) && workspace && !upper_only && p.kpad > 0) {
         const SkPlan q = sk_plan_wide(n, k_dim);
         GRF_REQUIRE_GRID(q.grid, 512, "gram_split_wide_kernel");
-        a.tickets = reinterpret_cast<int32_t *>(workspace);
-        a.slabs = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + kTicketBytes);
-        a.sk_units = q.units;
-        a.sk_kt = q.kt;
-        a.sk_total = q.total;
-        a.dp_rounds = q.dp_rounds;
-        a.xcd_slots = q.xcd_slots;
+        apply_plan(a, q, workspace);
         gram_split_wide_kernel<kSplitNST><<<(unsigned)q.grid, 512, 0, st>>>(a);
         GRF_CHECK_LAUNCH("gram_split_wide_kernel");
         return GRF_OK;
     }
-    static const int sk_env = env_int("GRF_DENSE_SK", -1);
-    const bool sk = workspace && (sk_env == 1 || (sk_env != 0 && p.tiles >= kCUs));
-    if (!workspace) {
-        p.n_split = 1;
-        p.n_whole = p.tiles;
-    }
-    if (sk) {
-        const SkPlan q = sk_plan(n, k_dim, BK);
+    if (workspace && p.tiles >= kCUs) {  // (stream-K by dense_gram's rule)
+        const SkPlan q = sk_plan(n, k_dim);
         GRF_REQUIRE_GRID(q.grid, 256, "gram_split_sk_kernel");
-        a.tickets = reinterpret_cast<int32_t *>(workspace);
-        a.slabs = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + kTicketBytes);
-        a.sk_units = q.units;
-        a.sk_kt = q.kt;
-        a.sk_total = q.total;
+        apply_plan(a, q, workspace);
         gram_split_sk_kernel<<<(unsigned)q.grid, 256, 0, st>>>(a);
         GRF_CHECK_LAUNCH("gram_split_sk_kernel");
         return GRF_OK;
     }
-    const int64_t split_tiles = p.tiles - p.n_whole;
-    const int64_t items = p.n_whole + split_tiles * p.n_split;
+    if (!workspace) p.whole_tiles_only();
+    const int64_t items = apply_plan(a, p, workspace);
     GRF_REQUIRE_GRID(items, 256, "gram_split_mfma_kernel");
-    a.tickets = split_tiles > 0 ? reinterpret_cast<int32_t *>(workspace) : nullptr;
-    a.slabs = split_tiles > 0 ? reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + kTicketBytes) : nullptr;
-    a.n_whole = p.n_whole;
-    a.k_split = p.k_split;
-    a.n_split = p.n_split;
     gram_split_mfma_kernel<<<(unsigned)items, 256, 0, st>>>(a);
     GRF_CHECK_LAUNCH("gram_split_mfma_kernel");
     return GRF_OK;
 }
 
-// ---- the planes path
-int64_t planes_row_bytes(int64_t k_dim) { return cdiv<int64_t>(k_dim, 16) * kPlaneBytes; }
+}  // namespace
+}  // namespace grf
 
-int32_t split_planes(int64_t n, int64_t k_dim, const float *A, int64_t lda, void *P, int64_t ldp, grf_stream_t stream) {
+using namespace grf;
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+size_t grf_gram_dense_workspace_bytes(int64_t n, int64_t k_dim) { return dense_gram_workspace_bytes(n, k_dim); }
+
+int32_t grf_gram_dense_ws(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
+                          void *workspace, size_t workspace_bytes, grf_stream_t stream) {
+    return dense_gram(n, k_dim, A, lda, K, ldk, workspace, workspace_bytes, false, stream);
+}
+
+int32_t grf_gram_dense_upper(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
+                             grf_stream_t stream) {
+    return dense_gram(n, k_dim, A, lda, K, ldk, nullptr, 0, true, stream);
+}
+
+int32_t grf_gram_dense(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
+                       grf_stream_t stream) {
+    return dense_gram(n, k_dim, A, lda, K, ldk, nullptr, 0, false, stream);
+}
+
+size_t grf_gram_dense_split_workspace_bytes(int64_t n, int64_t k_dim) {
+    return dense_gram_split_workspace_bytes(n, k_dim);
+}
+
+int32_t grf_gram_dense_split(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
+                             void *workspace, size_t workspace_bytes, grf_stream_t stream) {
+    GRF_REQUIRE(workspace, GRF_EINVAL, "grf_gram_dense_split: workspace required");
+    return dense_gram_split(n, k_dim, A, lda, K, ldk, workspace, workspace_bytes, false, stream);
+}
+
+// grf_gram_dense_upper on the split products (the hub-column split's panel)
+int32_t grf_gram_dense_split_upper(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
+                                   grf_stream_t stream) {
+    return dense_gram_split(n, k_dim, A, lda, K, ldk, nullptr, 0, true, stream);
+}
+
+// ---- the planes path
+int64_t grf_planes_row_bytes(int64_t k_dim) { return cdiv<int64_t>(k_dim, kBK) * kPlaneBytes; }
+
+int32_t grf_split_planes(int64_t n, int64_t k_dim, const float *A, int64_t lda, void *P, int64_t ldp,
+                         grf_stream_t stream) {
     GRF_REQUIRE(n >= 0 && k_dim >= 0 && (n == 0 || (A && P)), GRF_EINVAL, "grf_split_planes: bad arguments");
-    const int64_t kt = cdiv<int64_t>(k_dim, 16);
-    GRF_REQUIRE(lda >= 16 * kt && lda % 4 == 0 && ((uintptr_t)A & 15) == 0, GRF_EINVAL,
+    const int64_t kt = cdiv<int64_t>(k_dim, kBK);
+    GRF_REQUIRE(lda >= kBK * kt && lda % 4 == 0 && ((uintptr_t)A & 15) == 0, GRF_EINVAL,
                 "grf_split_planes: lda must cover k_dim rounded up to 16 (zero-padded), A 16-byte aligned");
     GRF_REQUIRE(ldp >= kt * kPlaneBytes && ldp % 16 == 0 && ((uintptr_t)P & 15) == 0, GRF_EINVAL,
                 "grf_split_planes: ldp must cover %lld bytes, a multiple of 16, P 16-byte aligned",
@@ -1537,32 +1377,34 @@ int32_t split_planes(int64_t n, int64_t k_dim, const float *A, int64_t lda, void
     return GRF_OK;
 }
 
-int32_t densify_padded_planes(int64_t n_rows, int64_t cap, int64_t n_cols, const int32_t *cnt, const int32_t *idx,
-                              const float *val, void *P, int64_t ldp, grf_stream_t stream) {
+int32_t grf_densify_padded_planes(int64_t n_rows, int64_t cap, int64_t n_cols, const int32_t *cnt, const int32_t *idx,
+                                  const float *val, void *P, int64_t ldp, grf_stream_t stream) {
     GRF_REQUIRE(n_rows >= 0 && cap >= 1 && n_cols >= 0 && (n_rows == 0 || (cnt && idx && val && P)), GRF_EINVAL,
                 "grf_densify_padded_planes: bad arguments");
-    const int64_t kt = cdiv<int64_t>(n_cols, 16);
+    const int64_t kt = cdiv<int64_t>(n_cols, kBK);
     GRF_REQUIRE(ldp >= kt * kPlaneBytes && ldp % 16 == 0 && ((uintptr_t)P & 15) == 0, GRF_EINVAL,
                 "grf_densify_padded_planes: ldp must cover %lld bytes, a multiple of 16, P 16-byte aligned",
                 (long long)(kt * kPlaneBytes));
-    GRF_REQUIRE(16 * kt * (int64_t)sizeof(float) <= 160 * 1024, GRF_EUNSUPPORTED,
-                "grf_densify_padded_planes: a row of %lld floats does not fit one CU's LDS", (long long)(16 * kt));
+    GRF_REQUIRE(kBK * kt * (int64_t)sizeof(float) <= 160 * 1024, GRF_EUNSUPPORTED,
+                "grf_densify_padded_planes: a row of %lld floats does not fit one CU's LDS", (long long)(kBK * kt));
     if (n_rows == 0) return GRF_OK;
     GRF_REQUIRE_GRID(n_rows, 256, "densify_padded_planes_kernel");
-    densify_padded_planes_kernel<<<(unsigned)n_rows, 256, (size_t)(16 * kt) * sizeof(float), S(stream)>>>(
+    densify_padded_planes_kernel<<<(unsigned)n_rows, 256, (size_t)(kBK * kt) * sizeof(float), S(stream)>>>(
         cap, cnt, idx, val, kt, reinterpret_cast<unsigned char *>(P), ldp);
     GRF_CHECK_LAUNCH("densify_padded_planes_kernel");
     return GRF_OK;
 }
 
-// K from the planes: the wide items from 64 tile rows on, else the 128-tile kernel; workspace as dense_gram_split's
-int32_t dense_gram_planes(int64_t n, int64_t k_dim, const void *P, int64_t ldp, float *K, int64_t ldk,
-                          void *workspace, size_t workspace_bytes, grf_stream_t stream) {
+// K from the planes: the wide items from 64 tile rows on (wide_items), else the 128-tile kernel; workspace as
+// grf_gram_dense_split's
+int32_t grf_gram_dense_planes(int64_t n, int64_t k_dim, const void *P, int64_t ldp, float *K, int64_t ldk,
+                              void *workspace, size_t workspace_bytes, grf_stream_t stream) {
     GRF_REQUIRE(n >= 0 && k_dim >= 0 && K && ldk >= n && (n == 0 || P), GRF_EINVAL, "grf_gram_dense_planes: bad arguments");
-    GRF_REQUIRE(ldp >= planes_row_bytes(k_dim) && ldp % 16 == 0 && ((uintptr_t)P & 15) == 0, GRF_EINVAL,
+    GRF_REQUIRE(ldp >= grf_planes_row_bytes(k_dim) && ldp % 16 == 0 && ((uintptr_t)P & 15) == 0, GRF_EINVAL,
                 "grf_gram_dense_planes: ldp must cover the k-tiles' planes, a multiple of 16, P 16-byte aligned");
-    GRF_REQUIRE(ldk % 4 == 0 && ((uintptr_t)K & 15) == 0, GRF_EINVAL,
-                "grf_gram_dense_planes: ldk must be a multiple of 4 and K 16-byte aligned");
+    DenseArgs a{};
+    const int32_t rc = dense_args("grf_gram_dense_planes", n, k_dim, K, ldk, false, a);
+    if (rc != GRF_OK) return rc;
     if (n == 0 || k_dim == 0) {
         if (n) GRF_CHECK_HIP(hipMemset2DAsync(K, (size_t)ldk * sizeof(float), 0, (size_t)n * sizeof(float), (size_t)n,
                                               S(stream)));
@@ -1571,43 +1413,20 @@ int32_t dense_gram_planes(int64_t n, int64_t k_dim, const void *P, int64_t ldp, 
     GRF_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0 &&
                     workspace_bytes >= dense_gram_split_workspace_bytes(n, k_dim),
                 GRF_EINVAL, "grf_gram_dense_planes: workspace too small or not 256-byte aligned");
-    DenseArgs a{};
-    a.K = K;
-    a.n = n;
-    a.nt = cdiv<int64_t>(n, kTile);
-    a.ldk = ldk;
-    a.kpad = cdiv<int64_t>(k_dim, 16) * 16;
-    // the wide items from 64 tile rows on (the split path's rule, GRF_DENSE_WIDE as there), else 128-tiles
-    const int wide_env = env_int("GRF_DENSE_WIDE", -1);
-    if (!(wide_env == 1 || (wide_env != 0 && a.nt >= 64))) {
-        const DensePlan p = dense_plan(n, k_dim, 16);
-        const int64_t split_tiles = p.tiles - p.n_whole;
-        const int64_t items = p.n_whole + split_tiles * p.n_split;
+    const unsigned char *planes = reinterpret_cast<const unsigned char *>(P);
+    if (!wide_items(a.nt)) {
+        const int64_t items = apply_plan(a, dense_plan(n, k_dim), workspace);
         GRF_REQUIRE_GRID(items, 256, "gram_planes_tile_kernel");
-        a.tickets = split_tiles > 0 ? reinterpret_cast<int32_t *>(workspace) : nullptr;
-        a.slabs = split_tiles > 0 ? reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + kTicketBytes)
-                                  : nullptr;
-        a.n_whole = p.n_whole;
-        a.k_split = p.k_split;
-        a.n_split = p.n_split;
-        gram_planes_tile_kernel<<<(unsigned)items, 256, 0, S(stream)>>>(a, reinterpret_cast<const unsigned char *>(P),
-                                                                         ldp);
+        gram_planes_tile_kernel<<<(unsigned)items, 256, 0, S(stream)>>>(a, planes, ldp);
         GRF_CHECK_LAUNCH("gram_planes_tile_kernel");
         return GRF_OK;
     }
     const SkPlan q = sk_plan_wide(n, k_dim);
     GRF_REQUIRE_GRID(q.grid, 512, "gram_planes_wide_kernel");
-    a.tickets = reinterpret_cast<int32_t *>(workspace);
-    a.slabs = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + kTicketBytes);
-    a.sk_units = q.units;
-    a.sk_kt = q.kt;
-    a.sk_total = q.total;
-    a.dp_rounds = q.dp_rounds;
-    a.xcd_slots = q.xcd_slots;
-    gram_planes_wide_kernel<kSplitNST><<<(unsigned)q.grid, 512, 0, S(stream)>>>(
-        a, reinterpret_cast<const unsigned char *>(P), ldp);
+    apply_plan(a, q, workspace);
+    gram_planes_wide_kernel<kSplitNST><<<(unsigned)q.grid, 512, 0, S(stream)>>>(a, planes, ldp);
     GRF_CHECK_LAUNCH("gram_planes_wide_kernel");
     return GRF_OK;
 }
 
-}  // namespace grf
+}  // extern "C"
