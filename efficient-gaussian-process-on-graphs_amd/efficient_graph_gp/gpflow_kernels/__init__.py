@@ -2,11 +2,15 @@
 
 GPflow / TensorFlow are not installed in this image, so the two fast-GRF kernels
 are provided with the same constructor and ``K`` / ``K_diag`` / ``grf_kernel`` API
-backed by the GPU engine (numpy in, numpy out).  The exact / PoFM / TF-walker
-kernels of the reference are outside the GRF hot path and raise NotImplementedError.
+backed by the GPU engine (numpy in, numpy out), and so are the two exact walk-power
+(PoFM) kernels they estimate, on the device SpGEMM's exact step matrices.  The
+eigendecomposition / TF-walker kernels of the reference are outside the GRF hot path and
+raise NotImplementedError.
 """
 from .diffusion_kernel_fast_grf import GraphDiffusionFastGRFKernel
+from .diffusion_kernel_pofm import GraphDiffusionPoFMKernel
 from .general_kernel_fast_grf import GraphGeneralFastGRFKernel
+from .general_kernel_pofm import GraphGeneralPoFMKernel
 
 
 def _out_of_scope(name):
@@ -18,9 +22,7 @@ def _out_of_scope(name):
 
 
 GraphDiffusionKernel = _out_of_scope("GraphDiffusionKernel")
-GraphDiffusionPoFMKernel = _out_of_scope("GraphDiffusionPoFMKernel")
 GraphDiffusionGRFKernel = _out_of_scope("GraphDiffusionGRFKernel")
-GraphGeneralPoFMKernel = _out_of_scope("GraphGeneralPoFMKernel")
 
 __all__ = ["GraphDiffusionKernel", "GraphDiffusionPoFMKernel", "GraphDiffusionGRFKernel",
            "GraphDiffusionFastGRFKernel", "GraphGeneralPoFMKernel", "GraphGeneralFastGRFKernel"]

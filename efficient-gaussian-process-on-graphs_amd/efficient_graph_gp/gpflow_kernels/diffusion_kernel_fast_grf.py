@@ -27,7 +27,7 @@ def _softplus_inverse(y: float) -> float:
 class GraphDiffusionFastGRFKernel(torch.nn.Module):
     def __init__(self, adjacency_matrix, walks_per_node: int = 50, p_halt: float = 0.1, max_walk_length: int = 10,
                  beta: float = 2.0, sigma_f: float = 1.0, random_walk_seed: int = 42, normalize_laplacian: bool = True,
-                 use_tqdm: bool = False, *, rng: Optional[str] = None, device=None, **kwargs):
+                 use_tqdm: bool = False, *, rng: Optional[str] = None, device=None, step_matrices=None, **kwargs):
         super().__init__()
         adjacency_matrix = np.asarray(adjacency_matrix, dtype=np.float64)
         assert adjacency_matrix.shape[0] == adjacency_matrix.shape[1], "Adjacency matrix must be square."
@@ -43,9 +43,13 @@ class GraphDiffusionFastGRFKernel(torch.nn.Module):
         self.raw_sigma_f = torch.nn.Parameter(torch.tensor(_softplus_inverse(float(sigma_f)), dtype=torch.float64,
                                                            device=self.device))
         self._lap_mode = C.LAP_NUMPY_SAFE if normalize_laplacian else C.LAP_COMBINATORIAL
-        # the walks run on that Laplacian, built and walked on the device (no host round trip)
-        F = api.dense_step_tensor_device(adjacency_matrix, walks_per_node, p_halt, max_walk_length,
-                                         seed=random_walk_seed, rng=rng, device=device, laplacian_mode=self._lap_mode)
+        if step_matrices is not None:  # (the PoFM subclass's exact steps, already on the device)
+            F = step_matrices
+        else:
+            # the walks run on that Laplacian, built and walked on the device (no host round trip)
+            F = api.dense_step_tensor_device(adjacency_matrix, walks_per_node, p_halt, max_walk_length,
+                                             seed=random_walk_seed, rng=rng, device=device,
+                                             laplacian_mode=self._lap_mode)
         self._steps = DenseSteps(F, get_engine(device))
 
     @property

@@ -48,7 +48,9 @@ class GraphGeneralFastGRFKernel(torch.nn.Module):
         self.modulator_vector = torch.nn.Parameter(torch.tensor(init, dtype=torch.float64, device=self.device))
         self._lap_mode = None
         if step_matrices is not None:
-            F = torch.as_tensor(np.asarray(step_matrices, dtype=np.float64))
+            # (a tensor -- the PoFM subclass's exact steps, already on the device -- is taken as it is)
+            F = step_matrices if torch.is_tensor(step_matrices) else \
+                torch.as_tensor(np.asarray(step_matrices, dtype=np.float64))
         elif ablation:
             F = api.dense_step_tensor_device(adjacency_matrix, walks_per_node, p_halt, max_walk_length,
                                              seed=random_walk_seed, ablation=True, rng=rng, device=device)

@@ -10,6 +10,11 @@ reference's attribute, used for the cache) is copied to the host only when read.
 Cache format: the reference pickles a list of scipy matrices; this engine writes
 a binary ``.npz`` bundle (per step: indptr, indices, data, shape) under the same
 md5-keyed name with a ``.npz`` suffix, read back with ``allow_pickle=False``.
+
+``exact=True`` (keyword only, not in the reference) returns the exact step matrices [I, L, L^2, ...]
+instead -- the expectation of the walk estimator's, from the device SpGEMM (``GRFEngine.exact_steps``) -- in
+the same form; ``walks_per_node``, ``p_halt`` and the seed are then ignored, and the cache name is keyed
+``exact_{max_walk_length}`` so that it cannot collide with a walk cache.
 """
 import hashlib
 import os
@@ -31,7 +36,7 @@ class GraphPreprocessor:
     def __init__(self, adjacency_matrix: sp.csr_matrix, walks_per_node: int = 10, p_halt: float = 0.5,
                  max_walk_length: int = 10, random_walk_seed: int = 42, load_from_disk: bool = False,
                  use_tqdm: bool = True, cache_filename: Optional[str] = None, n_processes: int = None, *,
-                 rng: Optional[str] = None, device=None) -> None:
+                 rng: Optional[str] = None, device=None, exact: bool = False) -> None:
         if adjacency_matrix.shape[0] != adjacency_matrix.shape[1]:
             raise ValueError("Adjacency matrix must be square.")
         self.adj_matrix = adjacency_matrix
@@ -40,6 +45,7 @@ class GraphPreprocessor:
         self.max_walk_length = max_walk_length
         self.random_walk_seed = random_walk_seed
         self.use_tqdm = use_tqdm
+        self.exact = bool(exact)
         self.cache_filename = cache_filename or self._generate_cache_filename()
         self.n_processes = n_processes
         self.rng = rng
@@ -58,6 +64,8 @@ class GraphPreprocessor:
         A = sp.csr_matrix(self.adj_matrix)
         adj_hash = hashlib.md5(A.data.tobytes() + A.indices.tobytes() + A.indptr.tobytes()).hexdigest()[:8]
         params = f"{A.shape[0]}_{self.walks_per_node}_{self.p_halt}_{self.max_walk_length}_{self.random_walk_seed}"
+        if self.exact:
+            params = f"{A.shape[0]}_exact_{self.max_walk_length}"
         return f"experiments_sparse/step_matrices/step_matrices_{adj_hash}_{params}.npz"
 
     def _to_device(self, t):
@@ -78,9 +86,13 @@ class GraphPreprocessor:
         """Laplacian -> walks -> step matrices on the GPU (reference :88-115); returns device-resident
         linear operators over torch CSR views of the device buffers (values cast to float32)."""
         self._step_scipy = None
-        self._step_device = api.sparse_step_matrices_device(
-            self.adj_matrix, self.walks_per_node, self.p_halt, self.max_walk_length, seed=self.random_walk_seed,
-            n_processes=self.n_processes, rng=self.rng, device=self.device, laplacian=True)
+        if self.exact:
+            self._step_device = api.exact_step_matrices_device(self.adj_matrix, self.max_walk_length, laplacian=True,
+                                                               device=self.device)
+        else:
+            self._step_device = api.sparse_step_matrices_device(
+                self.adj_matrix, self.walks_per_node, self.p_halt, self.max_walk_length, seed=self.random_walk_seed,
+                n_processes=self.n_processes, rng=self.rng, device=self.device, laplacian=True)
         if save_to_disk:
             self.save_step_matrices(self.step_matrices_scipy, self.cache_filename)
         n = self.adj_matrix.shape[0]

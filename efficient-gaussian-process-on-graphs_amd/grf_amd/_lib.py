@@ -26,6 +26,9 @@ RNG_PCG64, RNG_PHILOX = 0, 1
 LOAD_CUMULATIVE, LOAD_NONCUMULATIVE, LOAD_ABLATION = 0, 1, 2
 NORM_DIV, NORM_MUL_RECIP = 0, 1
 REC_LINE, REC_PACKED, REC_SLOT = 128, 12, 32
+# grf_spgemm_*'s per-row path thresholds (include/grf.h GRF_SPGEMM_*): products sorted in LDS up to the first,
+# output entries per LDS accumulator of the larger rows, and the bounds of those rows' wave count
+SPGEMM_SORT_PRODUCTS, SPGEMM_ACC_SLOTS, SPGEMM_BIG_MIN_WAVES, SPGEMM_BIG_MAX_WAVES = 1024, 4096, 8, 256
 ABI_VERSION = 9  # include/grf.h GRF_ABI_VERSION: argument lists change between revisions
 
 
@@ -146,6 +149,11 @@ SIGNATURES = {
     "grf_dense_steps_phi": (_i32, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "grf_dense_steps_grad_workspace_bytes": (_sz, [_i64, _i32]),
     "grf_dense_steps_grad": (_i32, [_i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    # C = A B, CSR x CSR -> CSR in fp64: the exact step matrices M_l = M_{l-1} L
+    "grf_spgemm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "grf_spgemm_csr_count": (_i32, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "grf_spgemm_csr_fill": (_i32, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                   _vp]),
 }
 
 _lib = None

@@ -100,6 +100,17 @@ def sparse_step_matrices_device(walk_matrix, num_walks, p_halt, max_walk_length,
     return eng.step_matrices(eng.steps(slots, C.NORM_MUL_RECIP))
 
 
+def exact_step_matrices_device(adj, max_walk_length, laplacian: bool = True, device=None) -> list:
+    """The exact step matrices [I, W, W^2, ...] (``max_walk_length`` of them) as device CSR (fp64 and fp32
+    values), W the normalised Laplacian of ``adj`` (laplacian=True) or ``adj`` itself: what the walk
+    estimator's step matrices are the expectation of, and the tensor the reference's PoFM kernels are built on
+    (compute_pstep_walk_matrix, gpflow_kernels/general_kernel_pofm.py:7-42), on the device SpGEMM."""
+    eng = get_engine(device)
+    A = _canonical_csr(adj)  # (sorted, duplicate-free rows: what the SpGEMM takes)
+    G = eng.laplacian(A) if laplacian else eng.to_device(A)
+    return eng.exact_steps(G, int(max_walk_length))
+
+
 def sparse_features(adj, modulator_vector, walks_per_node, p_halt, max_walk_length, *, n_processes=None, rng=None,
                     device=None, seed=None) -> DeviceCSR:
     """Phi = sum_l f_l M_l on the normalised Laplacian (graph_kernels_sparse/fast_grf_kernel_general.py:42-52)."""
@@ -185,6 +196,21 @@ def dense_step_tensor_device(walk_matrix, num_walks, p_halt, max_walk_length, se
     slots = _dense_slots(eng, G, num_walks, p_halt, max_walk_length, seed, n_processes, ablation, rng)
     st = eng.steps(slots, C.NORM_DIV)
     return eng.steps_dense(st)
+
+
+def exact_step_tensor_device(adj, max_walk_length, laplacian_mode=C.LAP_NUMPY_SAFE, device=None) -> torch.Tensor:
+    """compute_pstep_walk_matrix(laplacian, max_walk_length) (gpflow_kernels/general_kernel_pofm.py:7-42) as
+    an (N, N, L) float64 tensor on the device: the exact steps of ``GRFEngine.exact_steps`` on the Laplacian
+    of the given mode (LAP_NONE: ``adj`` itself), densified."""
+    eng = get_engine(device)
+    steps = eng.exact_steps(dense_walk_matrix(adj, laplacian_mode, device), int(max_walk_length))
+    n = steps[0].n_rows
+    F = torch.zeros((n, n, len(steps)), dtype=torch.float64, device=eng.device)
+    rows = torch.arange(n, device=eng.device)
+    for l, M in enumerate(steps):
+        r = torch.repeat_interleave(rows, M.ptr[1:] - M.ptr[:-1], output_size=M.nnz)
+        F[r, M.idx[:M.nnz].long(), l] = M.val[:M.nnz]
+    return F
 
 
 def dense_step_tensor(walk_matrix, num_walks, p_halt, max_walk_length, seed=None, n_processes=None, ablation=False,

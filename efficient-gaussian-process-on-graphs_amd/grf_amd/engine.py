@@ -1035,6 +1035,60 @@ class GRFEngine:
                    out.stride(0), self.stream), "grf_spmm_csr")
         return out
 
+    # ------------------------------------------------- sparse x sparse: the exact step matrices
+    SPGEMM_ENTRY_BYTES = 16  # an output entry: int32 column, float64 and float32 value
+
+    def _spgemm(self, A: DeviceCSR, B: DeviceCSR, max_nnz: Optional[int], what: str) -> DeviceCSR:
+        if A.n_cols != B.n_rows:
+            raise ValueError(f"spgemm: A is {A.n_rows} x {A.n_cols} but B has {B.n_rows} rows")
+        a_val = A.val if A.val is not None else A.val32.double()
+        b_val = B.val if B.val is not None else B.val32.double()
+        n, n_mid, n_cols = A.n_rows, A.n_cols, B.n_cols
+        ws = self._ws(self.lib.grf_spgemm_workspace_bytes(n, n_mid, n_cols))
+        cnt = self._empty(n, torch.int32)
+        C.check(self.lib.grf_spgemm_csr_count(n, n_mid, n_cols, _p(A.ptr), _p(A.idx), _p(B.ptr), _p(B.idx), _p(cnt),
+                                              _p(ws), ws.numel(), self.stream), "grf_spgemm_csr_count")
+        ptr = self._empty(n + 1, torch.int64)
+        sws = self._ws(self.lib.grf_scan_workspace_bytes(n))
+        C.check(self.lib.grf_scan_counts(n, _p(cnt), _p(ptr), _p(sws), sws.numel(), self.stream), "grf_scan_counts")
+        nnz = int(ptr[-1].item())  # (set-up, as preprocessing is: the one host read per product)
+        if max_nnz is None:
+            max_nnz = torch.cuda.mem_get_info(self.device)[0] // self.SPGEMM_ENTRY_BYTES
+        if nnz > max_nnz:
+            raise ValueError(f"{what} has nnz = {nnz}, more than max_nnz = {int(max_nnz)}")
+        idx = self._empty(max(nnz, 1), torch.int32)
+        val = self._empty(max(nnz, 1), torch.float64)
+        val32 = self._empty(max(nnz, 1), torch.float32)
+        C.check(self.lib.grf_spgemm_csr_fill(n, n_mid, n_cols, _p(A.ptr), _p(A.idx), _p(a_val), _p(B.ptr), _p(B.idx),
+                                             _p(b_val), _p(ptr), _p(idx), _p(val), _p(val32), _p(ws), ws.numel(),
+                                             self.stream), "grf_spgemm_csr_fill")
+        return DeviceCSR(n, n_cols, ptr, idx, val, val32, nnz)
+
+    def spgemm(self, A: DeviceCSR, B: DeviceCSR, max_nnz: Optional[int] = None) -> DeviceCSR:
+        """C = A B (CSR x CSR -> compact CSR, fp64 and fp32 values, ``nnz`` known) by the fixed rule of
+        include/grf.h grf_spgemm_csr_*: structural pattern (exact-zero sums kept), columns ascending, every
+        entry summed from +0.0 in the order of A's row entries without FMA -- scipy's ``A @ B`` to the bit."""
+        return self._spgemm(A, B, max_nnz, "spgemm: the product")
+
+    def exact_steps(self, G: DeviceCSR, max_walk_length: int, max_nnz: Optional[int] = None) -> list[DeviceCSR]:
+        """The exact step matrices [I, G, G^2, ...] (``max_walk_length`` of them, M_l = M_{l-1} G: the
+        reference's compute_pstep_walk_matrix, general_kernel_pofm.py:7-42) as device CSR -- what the walk
+        estimator's M_l are the expectation of.  A power with more than ``max_nnz`` entries (default: what
+        fits in free device memory) raises ValueError before it is allocated."""
+        if G.n_rows != G.n_cols:
+            raise ValueError("exact_steps: the walk matrix must be square")
+        if max_walk_length < 1:
+            raise ValueError("exact_steps: max_walk_length must be at least 1")
+        n = G.n_rows
+        ar = torch.arange(n + 1, dtype=torch.int64, device=self.device)
+        M = DeviceCSR(n, n, ar, ar[:n].to(torch.int32), torch.ones(n, dtype=torch.float64, device=self.device),
+                      torch.ones(n, dtype=torch.float32, device=self.device), n)
+        steps = [M]
+        for l in range(1, int(max_walk_length)):
+            M = self._spgemm(M, G, max_nnz, f"exact_steps: step {l}")
+            steps.append(M)
+        return steps
+
     def gram_matvec(self, phi: DeviceCSR, V: torch.Tensor, rows=None, cols=None, phi_t: Optional[DeviceCSR] = None,
                     noise: float = 0.0) -> torch.Tensor:
         """K[rows, cols] V = Phi[rows] (Phi[cols]^T V) (+ noise V when rows == cols), K never formed."""

@@ -71,7 +71,7 @@ enum grf_norm {
 /* The ABI revision of this header: grf_version() returns it, and a binding must refuse a library whose
  * revision differs (argument lists, or -- ABI 7 -- the GRF_RNG_PHILOX stream, change between revisions;
  * ABI 8 added grf_phi_row_shifts_padded and grf_gram_sparse_cols_padded; ABI 9 the marginal likelihood's
- * grf_cg_gram_solve_lanczos_f64 and grf_steps_frob_f64). */
+ * grf_cg_gram_solve_lanczos_f64 and grf_steps_frob_f64; grf_spgemm_* came later, purely additive). */
 #define GRF_ABI_VERSION 9
 
 const char *grf_last_error(void);
@@ -639,6 +639,43 @@ int32_t grf_dense_to_csr_count(int64_t n_rows, int64_t n_cols, const float *K, i
                                grf_stream_t stream);
 int32_t grf_dense_to_csr_fill(int64_t n_rows, int64_t n_cols, const float *K, int64_t ldk, const int64_t *out_ptr,
                               int32_t *out_idx, double *out_val, grf_stream_t stream);
+
+/* ------------------------------------------- sparse x sparse: the exact step matrices' producer
+ * C = A B, CSR x CSR -> CSR in fp64 (A: n_rows x n_mid, B: n_mid x n_cols; the project's CSR: int64 row
+ * pointers, int32 columns ascending and unique per row, float64 values; rows may be empty; every dimension
+ * up to 2^31 - 1).  Chained as M_l = M_{l-1} L from M_0 = I it gives the exact walk-power tensor
+ * [I, L, L^2, ...] of the reference's compute_pstep_walk_matrix (general_kernel_pofm.py:7-42), which its
+ * GraphGeneralPoFMKernel / GraphDiffusionPoFMKernel are built on.
+ *
+ * The result is fixed to the bit: row i's pattern is the union of the patterns of B's rows k over the stored
+ * entries (i, k) of A, columns ascending, exact-zero sums KEPT (structural pattern); c_ij starts from +0.0
+ * and adds RN(a_ik b_kj) one product at a time in the order of A's row entries (ascending k), multiply and
+ * add rounded separately (no FMA).  This is Gustavson's order and scipy's: the bits of scipy's `A @ B` after
+ * sort_indices, apart from exact-zero sums, which scipy may drop.  No floating-point atomics: two calls give
+ * the same bits.
+ *
+ * Same convention as grf_phi_steps_csr_count / _fill: _count writes the row lengths (int32 [n_rows]; scan
+ * them with grf_scan_counts), _fill writes the rows at c_ptr (c_val32, the values rounded once to float32,
+ * may be NULL).  Both need grf_spgemm_workspace_bytes(n_rows, n_mid, n_cols) bytes of workspace, run
+ * asynchronously on `stream` and read nothing back.  Per output row the kernels choose, on the device, by
+ * the row's product count P = sum over A's entries (i, k) of len(B[k]): up to GRF_SPGEMM_SORT_PRODUCTS the
+ * products are sorted by (column, sequence) in LDS and summed in order; larger rows go to a fixed set of
+ * waves (between GRF_SPGEMM_BIG_MIN_WAVES and GRF_SPGEMM_BIG_MAX_WAVES, by n_cols) that mark the columns in
+ * a bitmap of n_cols bits each and accumulate GRF_SPGEMM_ACC_SLOTS output entries at a time in LDS. */
+#define GRF_SPGEMM_SORT_PRODUCTS 1024
+#define GRF_SPGEMM_ACC_SLOTS 4096
+#define GRF_SPGEMM_BIG_MIN_WAVES 8
+#define GRF_SPGEMM_BIG_MAX_WAVES 256
+size_t grf_spgemm_workspace_bytes(int64_t n_rows, int64_t n_mid, int64_t n_cols);
+/* general_kernel_pofm.py:7-42 (the pattern of current_power @ adj_matrix) */
+int32_t grf_spgemm_csr_count(int64_t n_rows, int64_t n_mid, int64_t n_cols, const int64_t *a_ptr, const int32_t *a_idx,
+                             const int64_t *b_ptr, const int32_t *b_idx, int32_t *row_cnt, void *workspace,
+                             size_t workspace_bytes, grf_stream_t stream);
+/* general_kernel_pofm.py:7-42 (current_power @ adj_matrix itself) */
+int32_t grf_spgemm_csr_fill(int64_t n_rows, int64_t n_mid, int64_t n_cols, const int64_t *a_ptr, const int32_t *a_idx,
+                            const double *a_val, const int64_t *b_ptr, const int32_t *b_idx, const double *b_val,
+                            const int64_t *c_ptr, int32_t *c_idx, double *c_val, float *c_val32, void *workspace,
+                            size_t workspace_bytes, grf_stream_t stream);
 
 #ifdef __cplusplus
 }
