@@ -239,11 +239,15 @@ __device__ __forceinline__ void gram_windows(const GramStream &g, int32_t w0, in
     }
 }
 
-// int64 fixed point (scale 2^sh) -> float: two exact-width converts, one fma, one ldexp
-// (|error| <= 1.5 ulp of the result; deterministic)
+// int64 fixed point (scale 2^sh, |a| < 2^62) -> float: the two words converted, one fma, one ldexp
+// (|error| <= 1.5 ulp of the result; deterministic).  The low word counts as SIGNED, a = hi 2^32 + lo with
+// |lo| <= 2^31 (hi takes lo's sign bit back: two integer ops): as an unsigned word, a small negative sum has
+// hi = -1 and lo just below 2^32, whose float rounding (up to 2^7 units) is far above the sum's own ulp
+// (-2 came out as +0).
 __device__ inline float fx_to_float(unsigned long long a, int sh) {
-    const float hi = (float)(int)(a >> 32), lo = (float)(unsigned)(a & 0xffffffffull);
-    return ldexpf(fmaf(hi, 4294967296.0f, lo), -sh);
+    const int lo = (int)(unsigned)(a & 0xffffffffull);
+    const int hi = (int)(a >> 32) - (lo >> 31);
+    return ldexpf(fmaf((float)hi, 4294967296.0f, (float)lo), -sh);
 }
 
 // LDS bytes of one gram_sparse_kernel workgroup (W int64 counters + per-wave stream state):
@@ -476,7 +480,8 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
         for (int64_t i = n4 * 4 + tid; i < wlen; i += 64 * kWaves)
             krow[i] = addk ? fx_to_float(acc[i], sh) + krow[i] : fx_to_float(acc[i], sh);
     } else {
-        for (int64_t i = tid; i < wlen; i += 64 * kWaves)
+        // (from the row's sub-band on, as the vector path: the columns before it hold partial sums)
+        for (int64_t i = c_lo + tid; i < wlen; i += 64 * kWaves)
             krow[i] = addk ? fx_to_float(acc[i], sh) + krow[i] : fx_to_float(acc[i], sh);
     }
 }

@@ -7,7 +7,8 @@ Tolerances
     (fp32 rounding of Phi's entries, fp32 output rounding, and the sparse kernel's
     int64 fixed-point resolution of 2^-50 per term), and relative Frobenius error <= 1e-6.  The sparse Gram kernel is
     much tighter than that (fp32 rounding of Phi's entries, then an exact
-    fixed-point sum rounded once), the MFMA dense Gram is an fp32 FMA chain.
+    fixed-point sum rounded once): tests/test_gpu_gram_kernels.py holds it to its exact bits against the numpy
+    restatement of tests/gram_reference.py.  The MFMA dense Gram is an fp32 FMA chain.
 """
 import numpy as np
 import pytest
