@@ -1248,8 +1248,9 @@ int32_t dense_gram(int64_t n, int64_t k_dim, const float *A, int64_t lda, float 
     hipStream_t st = S(stream);
     // stream-K when the tiles fill at least half the slots (every slot then takes >= half a tile of k, so a
     // split tile has <= 3 pieces): n = 4096 0.68 -> 0.78, C2 0.83 -> 0.86 of the MFMA peak; at C3 (253 tiles)
-    // even, below it the per-tile splits win (profiles/r04_dense_ab.txt).
-    if (p.tiles >= kCUs) {
+    // even, below it the per-tile splits win (profiles/r04_dense_ab.txt).  k_dim = 0 has no k-tile units to deal out
+    // (sk_plan's grid is 0): the whole tiles below write the zero K.
+    if (p.tiles >= kCUs && p.kpad > 0) {
         const SkPlan q = sk_plan(n, k_dim);
         if (workspace && workspace_bytes >= q.ws_bytes && ((uintptr_t)workspace & 255) == 0) {
             GRF_REQUIRE_GRID(q.grid, 256, "gram_dense_sk_kernel");
@@ -1299,7 +1300,7 @@ int32_t dense_gram_split(int64_t n, int64_t k_dim, const float *A, int64_t lda, 
         GRF_CHECK_LAUNCH("gram_split_wide_kernel");
         return GRF_OK;
     }
-    if (workspace && p.tiles >= kCUs) {  // (stream-K by dense_gram's rule)
+    if (workspace && p.tiles >= kCUs && p.kpad > 0) {  // (stream-K by dense_gram's rule)
         const SkPlan q = sk_plan(n, k_dim);
         GRF_REQUIRE_GRID(q.grid, 256, "gram_split_sk_kernel");
         apply_plan(a, q, workspace);
