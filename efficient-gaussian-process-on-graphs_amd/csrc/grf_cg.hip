@@ -19,6 +19,8 @@
 //                               lane groups split the nonzeros, fixed-order sums.
 //   cg_* kernels                column reductions (fp64, fixed order, last block
 //                               finalises) and the vector updates of linear_cg.
+// The recurrence (cg_solve_impl) takes its matvec as a functor: GramMatVec is the two SpMMs above, PolyMatVec
+// the two Horner chains of the walk polynomial (grf_poly.hip: K = S_T p(G) p(G)^T S_T^T, no Phi formed).
 // All CG kernels read a device `done` flag first: once the stopping rule fires
 // the rest of the enqueued iterations are no-ops, so the host only polls the
 // flag and never serialises the stream per iteration.
@@ -29,6 +31,7 @@
 #include <algorithm>
 
 #include "grf_common.h"
+#include "grf_poly.h"
 
 namespace grf {
 
@@ -470,8 +473,14 @@ __global__ __launch_bounds__(256) void cg_out_kernel(int64_t n, int32_t S, const
     out[r * ldo + c] = X[i] * (T)st.rhs_norm[c];
 }
 
+// the recurrence's own buffers (every matvec's layout starts from these names)
+struct CgBase {
+    size_t R, P, Y, X, part, dbl, i32;
+};
+
 struct CgLayout {
-    size_t R, P, Y, X, W, part, dbl, i32, seg1, seg2, total;
+    CgBase base;
+    size_t W, seg1, seg2, total;
     int32_t tw1, nt1, tw2, nt2;  // column tiles of Phi_t^T (over the n_sys rows of P) and Phi_t (over W)
 };
 
@@ -479,14 +488,14 @@ static CgLayout cg_layout(int64_t n_sys, int64_t n_cols, int32_t S, size_t elem)
     CgLayout l{};
     size_t o = 0;
     const size_t vec = al256((size_t)n_sys * S * elem);
-    l.R = o; o += vec;
-    l.P = o; o += vec;
-    l.Y = o; o += vec;
-    l.X = o; o += vec;
+    l.base.R = o; o += vec;
+    l.base.P = o; o += vec;
+    l.base.Y = o; o += vec;
+    l.base.X = o; o += vec;
     l.W = o; o += al256((size_t)n_cols * S * elem);
-    l.part = o; o += al256((size_t)kRedBlocks * S * sizeof(double));
-    l.dbl = o; o += al256((size_t)5 * S * sizeof(double));
-    l.i32 = o; o += al256((size_t)(2 * S + 8) * sizeof(int32_t));
+    l.base.part = o; o += al256((size_t)kRedBlocks * S * sizeof(double));
+    l.base.dbl = o; o += al256((size_t)5 * S * sizeof(double));
+    l.base.i32 = o; o += al256((size_t)(2 * S + 8) * sizeof(int32_t));
     l.tw1 = spmm_tile_rows(n_sys, S, elem);
     l.nt1 = l.tw1 ? (int32_t)cdiv<int64_t>(n_sys, l.tw1) : 1;
     l.tw2 = spmm_tile_rows(n_cols, S, elem);
@@ -497,23 +506,100 @@ static CgLayout cg_layout(int64_t n_sys, int64_t n_cols, int32_t S, size_t elem)
     return l;
 }
 
+// mvms = (Phi_t Phi_t^T + s2 I) p as two SpMMs: W = Phi_t^T P, Y = Phi_t W + s2 P
 template <typename T>
-static int32_t cg_solve_impl(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
-                             const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
-                             const float *t_val, double noise, const T *rhs, int64_t ld_rhs, int32_t n_rhs,
+struct GramMatVec {
+    int64_t n_sys;
+    const int64_t *ptr;
+    const int32_t *idx;
+    const float *val;
+    const int32_t *row_map;
+    int64_t n_cols;
+    const int64_t *t_ptr;
+    const int32_t *t_idx;
+    const float *t_val;
+    double noise;
+    CgLayout l;
+    T *W = nullptr;
+    int64_t *seg1 = nullptr, *seg2 = nullptr;
+
+    // the column-tile plans of the two SpMMs (once per solve)
+    int32_t prepare(char *w, hipStream_t sm) {
+        W = (T *)(w + l.W);
+        seg1 = l.tw1 ? (int64_t *)(w + l.seg1) : nullptr;
+        seg2 = l.tw2 ? (int64_t *)(w + l.seg2) : nullptr;
+        int32_t rc;
+        if (seg1 && (rc = spmm_plan(n_cols, t_ptr, t_idx, nullptr, l.tw1, l.nt1, seg1, sm)) != GRF_OK) return rc;
+        if (seg2 && (rc = spmm_plan(n_sys, ptr, idx, row_map, l.tw2, l.nt2, seg2, sm)) != GRF_OK) return rc;
+        return GRF_OK;
+    }
+
+    int32_t operator()(const T *P, T *Y, int32_t Sn, const int32_t *done, hipStream_t sm) const {
+        const int32_t rc = spmm_dispatch<T>(n_cols, t_ptr, t_idx, t_val, nullptr, P, Sn, Sn, W, Sn, nullptr, 0, T(0),
+                                            done, sm, seg1, l.nt1);
+        if (rc != GRF_OK) return rc;
+        return spmm_dispatch<T>(n_sys, ptr, idx, val, row_map, W, Sn, Sn, Y, Sn, P, Sn, (T)noise, done, sm, seg2,
+                                l.nt2);
+    }
+};
+
+struct CgPolyLayout {
+    CgBase base;
+    size_t W, H0, H1, total;
+};
+
+static CgPolyLayout cg_poly_layout(int64_t n_sys, int64_t n, int32_t S) {
+    CgPolyLayout l{};
+    size_t o = 0;
+    const size_t vec = al256((size_t)n_sys * S * sizeof(double)), blk = al256((size_t)n * S * sizeof(double));
+    l.base.R = o; o += vec;
+    l.base.P = o; o += vec;
+    l.base.Y = o; o += vec;
+    l.base.X = o; o += vec;
+    l.W = o; o += blk;
+    l.H0 = o; o += blk;
+    l.H1 = o; o += blk;
+    l.base.part = o; o += al256((size_t)kRedBlocks * S * sizeof(double));
+    l.base.dbl = o; o += al256((size_t)5 * S * sizeof(double));
+    l.base.i32 = o; o += al256((size_t)(2 * S + 8) * sizeof(int32_t));
+    l.total = o;
+    return l;
+}
+
+// mvms = (S_T p(G) p(G)^T S_T^T + s2 I) p as two Horner chains with the walk matrix: W = p(G^T) S_T^T P (read
+// from P through inv_map), then Y = S_T p(G) W + s2 P (the last step on the training rows only)
+struct PolyMatVec {
+    int64_t n_sys;
+    PolyOp g, gt;
+    const int32_t *row_map, *inv_map;
+    double noise;
+    CgPolyLayout l;
+    double *W = nullptr, *H0 = nullptr, *H1 = nullptr;
+
+    int32_t prepare(char *w, hipStream_t) {
+        W = (double *)(w + l.W);
+        H0 = (double *)(w + l.H0);
+        H1 = (double *)(w + l.H1);
+        return GRF_OK;
+    }
+
+    int32_t operator()(const double *P, double *Y, int32_t Sn, const int32_t *done, hipStream_t sm) const {
+        const int32_t rc = poly_chain(gt, inv_map, P, Sn, Sn, nullptr, gt.n, W, Sn, nullptr, 0, 0.0, H0, H1, done, sm);
+        if (rc != GRF_OK) return rc;
+        return poly_chain(g, nullptr, W, Sn, Sn, row_map, n_sys, Y, Sn, P, Sn, noise, H0, H1, done, sm);
+    }
+};
+
+// linear_cg on n_sys x n_rhs systems; `mv` computes Y = (K + s2 I) P on the stream (the checks of its own
+// operands are the caller's); `l`: where the recurrence's buffers lie in the workspace
+template <typename T, typename MatVec>
+static int32_t cg_solve_impl(int64_t n_sys, MatVec &mv, const CgBase &l, const T *rhs, int64_t ld_rhs, int32_t n_rhs,
                              double tolerance, int32_t max_iter, T *x, int64_t ldx, void *workspace,
-                             size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream,
-                             double *coef = nullptr, int64_t ld_coef = 0) {
-    GRF_REQUIRE(n_sys > 0 && n_cols > 0 && ptr && t_ptr && rhs && x, GRF_EINVAL, "grf_cg_gram_solve: bad arguments");
-    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_cg_gram_solve: n_rhs must be in [1, %d]",
-                kMaxRhs);
-    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_cg_gram_solve: bad strides");
-    const CgLayout l = cg_layout(n_sys, n_cols, n_rhs, sizeof(T));
-    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL, "grf_cg_gram_solve: workspace too small (%zu < %zu)",
-                workspace_bytes, l.total);
+                             int32_t *iters_out, double *resid_out, grf_stream_t stream, double *coef = nullptr,
+                             int64_t ld_coef = 0) {
     hipStream_t sm = S(stream);
     char *w = (char *)workspace;
-    T *R = (T *)(w + l.R), *P = (T *)(w + l.P), *Y = (T *)(w + l.Y), *X = (T *)(w + l.X), *W = (T *)(w + l.W);
+    T *R = (T *)(w + l.R), *P = (T *)(w + l.P), *Y = (T *)(w + l.Y), *X = (T *)(w + l.X);
     const int32_t Sn = n_rhs;
     CgState st;
     double *d = (double *)(w + l.dbl);
@@ -534,9 +620,7 @@ static int32_t cg_solve_impl(int64_t n_sys, const int64_t *ptr, const int32_t *i
     const int32_t k_check = std::min(10, max_iter - 1);
     int32_t rc0;
 
-    int64_t *seg1 = l.tw1 ? (int64_t *)(w + l.seg1) : nullptr, *seg2 = l.tw2 ? (int64_t *)(w + l.seg2) : nullptr;
-    if (seg1 && (rc0 = spmm_plan(n_cols, t_ptr, t_idx, nullptr, l.tw1, l.nt1, seg1, sm)) != GRF_OK) return rc0;
-    if (seg2 && (rc0 = spmm_plan(n_sys, ptr, idx, row_map, l.tw2, l.nt2, seg2, sm)) != GRF_OK) return rc0;
+    if ((rc0 = mv.prepare(w, sm)) != GRF_OK) return rc0;
     cg_reduce_kernel<kFinNorm, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance);
     GRF_CHECK_LAUNCH("cg_reduce_kernel<norm>");
     cg_reduce_kernel<kFinInit, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance);
@@ -549,12 +633,8 @@ static int32_t cg_solve_impl(int64_t n_sys, const int64_t *ptr, const int32_t *i
     GRF_CHECK_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
     int32_t rc = GRF_OK;
     for (int32_t k = 0; k < max_iter && rc == GRF_OK; ++k) {
-        // mvms = (K + s2 I) p = Phi_t (Phi_t^T p) + s2 p
-        rc = spmm_dispatch<T>(n_cols, t_ptr, t_idx, t_val, nullptr, P, Sn, Sn, W, Sn, nullptr, 0, T(0), st.done, sm,
-                              seg1, l.nt1);
-        if (rc != GRF_OK) break;
-        rc = spmm_dispatch<T>(n_sys, ptr, idx, val, row_map, W, Sn, Sn, Y, Sn, P, Sn, (T)noise, st.done, sm, seg2,
-                              l.nt2);
+        // mvms = (K + s2 I) p
+        rc = mv(P, Y, Sn, st.done, sm);
         if (rc != GRF_OK) break;
         cg_reduce_kernel<kFinAlpha, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance);
         cg_reduce_kernel<kFinUpdate, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance);
@@ -605,6 +685,49 @@ static int32_t cg_solve_impl(int64_t n_sys, const int64_t *ptr, const int32_t *i
     (void)hipEventDestroy(ev[1]);
     (void)hipHostFree(h);
     return rc;
+}
+
+// the Phi-based solve: its argument checks, then the shared recurrence on the two SpMMs
+template <typename T>
+static int32_t cg_gram_solve(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                             const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
+                             const float *t_val, double noise, const T *rhs, int64_t ld_rhs, int32_t n_rhs,
+                             double tolerance, int32_t max_iter, T *x, int64_t ldx, void *workspace,
+                             size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream,
+                             double *coef = nullptr, int64_t ld_coef = 0) {
+    GRF_REQUIRE(n_sys > 0 && n_cols > 0 && ptr && t_ptr && rhs && x, GRF_EINVAL, "grf_cg_gram_solve: bad arguments");
+    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_cg_gram_solve: n_rhs must be in [1, %d]",
+                kMaxRhs);
+    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_cg_gram_solve: bad strides");
+    const CgLayout l = cg_layout(n_sys, n_cols, n_rhs, sizeof(T));
+    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL, "grf_cg_gram_solve: workspace too small (%zu < %zu)",
+                workspace_bytes, l.total);
+    GramMatVec<T> mv{n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, l};
+    return cg_solve_impl<T>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, iters_out,
+                            resid_out, stream, coef, ld_coef);
+}
+
+// the same recurrence on the walk polynomial (fp64 only)
+static int32_t cg_poly_solve(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                             const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
+                             const double *f, int32_t n_f, const int32_t *row_map, const int32_t *inv_map,
+                             double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs, double tolerance,
+                             int32_t max_iter, double *x, int64_t ldx, void *workspace, size_t workspace_bytes,
+                             int32_t *iters_out, double *resid_out, grf_stream_t stream, double *coef = nullptr,
+                             int64_t ld_coef = 0) {
+    GRF_REQUIRE(n_sys > 0 && n > 0 && g_ptr && gt_ptr && f && n_f >= 1 && row_map && inv_map && rhs && x, GRF_EINVAL,
+                "grf_cg_poly_solve: bad arguments");
+    GRF_REQUIRE(n < (1ll << 31) && n_sys < (1ll << 31), GRF_EUNSUPPORTED, "grf_cg_poly_solve: more than 2^31 rows");
+    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_cg_poly_solve: n_rhs must be in [1, %d]",
+                kMaxRhs);
+    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_cg_poly_solve: bad strides");
+    const CgPolyLayout l = cg_poly_layout(n_sys, n, n_rhs);
+    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL, "grf_cg_poly_solve: workspace too small (%zu < %zu)",
+                workspace_bytes, l.total);
+    PolyMatVec mv{n_sys, PolyOp{n, g_ptr, g_idx, g_val, f, n_f}, PolyOp{n, gt_ptr, gt_idx, gt_val, f, n_f}, row_map,
+                  inv_map, noise, l};
+    return cg_solve_impl<double>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace,
+                                 iters_out, resid_out, stream, coef, ld_coef);
 }
 
 }  // namespace grf
@@ -697,7 +820,7 @@ int32_t grf_cg_gram_solve(int64_t n_sys, const int64_t *ptr, const int32_t *idx,
                           const float *t_val, double noise, const float *rhs, int64_t ld_rhs, int32_t n_rhs,
                           double tolerance, int32_t max_iter, float *x, int64_t ldx, void *workspace,
                           size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream) {
-    return cg_solve_impl<float>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs, n_rhs,
+    return cg_gram_solve<float>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs, n_rhs,
                                 tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out, stream);
 }
 
@@ -706,7 +829,7 @@ int32_t grf_cg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *
                               const float *t_val, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream) {
-    return cg_solve_impl<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs,
+    return cg_gram_solve<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs,
                                  n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
                                  stream);
 }
@@ -718,9 +841,37 @@ int32_t grf_cg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const i
                                       int64_t ldx, void *workspace, size_t workspace_bytes, int32_t *iters_out,
                                       double *resid_out, double *coef, int64_t ld_coef, grf_stream_t stream) {
     GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_cg_gram_solve_lanczos_f64: bad coefficient buffer");
-    return cg_solve_impl<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs,
+    return cg_gram_solve<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs,
                                  n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
                                  stream, coef, ld_coef);
+}
+
+size_t grf_cg_poly_workspace_bytes(int64_t n_sys, int64_t n, int32_t n_rhs) {
+    return cg_poly_layout(n_sys, n, n_rhs).total;
+}
+
+int32_t grf_cg_poly_solve_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                              const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
+                              const double *f, int32_t n_f, const int32_t *row_map, const int32_t *inv_map,
+                              double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs, double tolerance,
+                              int32_t max_iter, double *x, int64_t ldx, void *workspace, size_t workspace_bytes,
+                              int32_t *iters_out, double *resid_out, grf_stream_t stream) {
+    return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
+                         ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
+                         stream);
+}
+
+int32_t grf_cg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                                      const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
+                                      const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
+                                      const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs,
+                                      int32_t n_rhs, double tolerance, int32_t max_iter, double *x, int64_t ldx,
+                                      void *workspace, size_t workspace_bytes, int32_t *iters_out, double *resid_out,
+                                      double *coef, int64_t ld_coef, grf_stream_t stream) {
+    GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_cg_poly_solve_lanczos_f64: bad coefficient buffer");
+    return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
+                         ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
+                         stream, coef, ld_coef);
 }
 
 #pragma GCC visibility pop

@@ -8,7 +8,7 @@ never densified.  Subclasses ``gpytorch.kernels.Kernel`` when gpytorch is instal
 """
 import torch
 
-from grf_amd.features import StepMatrices, feature_matrix, grf_kernel
+from grf_amd.features import StepMatrices, WalkPolynomial, feature_matrix, grf_kernel
 
 try:
     import gpytorch
@@ -29,16 +29,32 @@ class SparseGRFKernel(_Base):
     def modulator_vector(self):
         return self.raw_modulator_vector
 
-    def _step_set(self) -> StepMatrices:
+    def _operator(self):
+        """The WalkPolynomial this kernel was built on (``step_matrices_torch=<WalkPolynomial>``), else None."""
+        return self.step_matrices if isinstance(self.step_matrices, WalkPolynomial) else None
+
+    def _no_blocks(self, what: str):
+        return NotImplementedError(
+            f"SparseGRFKernel.{what} needs step matrices: on a WalkPolynomial K and Phi are never formed; use "
+            "SparseGraphGP.predict and SparseGraphGP.marginal_log_likelihood, which run on the operator")
+
+    def _step_set(self):
+        """The StepMatrices of the kernel's step matrices, or its WalkPolynomial."""
+        if self._operator() is not None:
+            return self.step_matrices
         if self._steps is None:
             self._steps = StepMatrices(self.step_matrices)
         return self._steps
 
     def forward(self, x1_idx=None, x2_idx=None, diag=False, **params):
         """K[x1, x2] (or its diagonal) = Phi[x1] Phi[x2]^T (reference :24-49)."""
+        if self._operator() is not None:
+            raise self._no_blocks("forward")
         return grf_kernel(self.modulator_vector, self._step_set(), x1_idx, x2_idx, diag)
 
     def _get_feature_matrix(self):
         """Phi as a torch sparse CSR tensor on the device (reference :51-61; not differentiable:
         gradients flow through ``forward``)."""
+        if self._operator() is not None:
+            raise self._no_blocks("_get_feature_matrix")
         return feature_matrix(self.modulator_vector, self._step_set())

@@ -17,7 +17,7 @@ Subclasses ``gpytorch.models.ExactGP`` when gpytorch is installed; otherwise a
 """
 import torch
 
-from grf_amd.engine import DeviceCSR, get_engine  # noqa: F401
+from grf_amd.engine import DeviceCSR, WalkPolynomial, get_engine  # noqa: F401
 from grf_amd.features import grf_marginal_log_likelihood, resolve_cg_tolerance
 
 from ..gptorch_kernels_sparse.sparse_grf_kernel import SparseGRFKernel
@@ -45,7 +45,9 @@ class SparseGraphGP(_Base):
             self.likelihood = likelihood
         self.x_train, self.y_train = x_train, y_train
         self.covar_module = SparseGRFKernel(max_walk_length=max_walk_length, step_matrices_torch=step_matrices)
-        self.num_nodes = step_matrices[0].shape[0]
+        # (step_matrices may be a WalkPolynomial: predict and marginal_log_likelihood then run on the exact
+        # kernel Phi = p(G) as a matrix-free operator)
+        self.num_nodes = (step_matrices if isinstance(step_matrices, WalkPolynomial) else step_matrices[0]).shape[0]
 
     def forward(self, x):
         if gpytorch is not None:
@@ -85,7 +87,10 @@ class SparseGraphGP(_Base):
         train_indices = self.x_train.int().flatten()
         test_indices = x_test.int().flatten()
         eng = get_engine(dev if dev.type == "cuda" else None)
-        phi = self._phi_csr(eng.device)
+        op = self.covar_module._operator()
+        if op is not None and op.engine.device != eng.device:
+            raise ValueError("predict: the walk operator lives on another device than x_test")
+        phi = op if op is not None else self._phi_csr(eng.device)
 
         noise_variance = _noise_value(self.likelihood)
         noise_std = torch.sqrt(torch.tensor(noise_variance, device=dev))
@@ -95,5 +100,6 @@ class SparseGraphGP(_Base):
         tolerance = resolve_cg_tolerance(tolerance)
         out, self.last_cg_iterations = eng.pathwise_predict(
             phi, train_indices.to(eng.device), test_indices.to(eng.device), self.y_train, noise_variance,
-            eps1_batch, eps2_batch, tolerance=tolerance, max_iter=max_iter, dtype=cg_dtype)
+            eps1_batch, eps2_batch, tolerance=tolerance, max_iter=max_iter, dtype=cg_dtype,
+            f=self.covar_module.modulator_vector if op is not None else None)
         return out.to(torch.float32)

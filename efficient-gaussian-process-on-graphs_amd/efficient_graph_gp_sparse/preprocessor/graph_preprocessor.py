@@ -25,7 +25,7 @@ import scipy.sparse as sp
 import torch
 
 from grf_amd import api
-from grf_amd.engine import get_engine
+from grf_amd.engine import WalkPolynomial, get_engine
 
 from ..utils_sparse import SparseLinearOperator
 
@@ -101,6 +101,13 @@ class GraphPreprocessor:
                                                          dtype=torch.float32))
             for M in self._step_device]
         return self.step_matrices_torch
+
+    def walk_operator(self) -> WalkPolynomial:
+        """The exact kernel's feature matrix Phi = sum_l f_l G^l of this graph's normalised Laplacian G as a
+        matrix-free operator (``max_walk_length`` terms): no walks, no powers of G, no cache.  Pass it to
+        ``SparseGraphGP(..., step_matrices=<operator>)`` for ``predict`` and ``marginal_log_likelihood``."""
+        eng = get_engine(self.device)
+        return WalkPolynomial(eng.laplacian(api._canonical_csr(self.adj_matrix)), self.max_walk_length, engine=eng)
 
     @staticmethod
     def from_scipy_csr(scipy_csr: sp.csr_matrix) -> torch.Tensor:

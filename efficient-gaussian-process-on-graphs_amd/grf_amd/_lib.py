@@ -154,6 +154,18 @@ SIGNATURES = {
     "grf_spgemm_csr_count": (_i32, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "grf_spgemm_csr_fill": (_i32, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
+    # the exact walk-power kernel as a matrix-free operator: Horner chains with the walk matrix, CG, gradient
+    "grf_poly_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "grf_poly_apply_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp,
+                                  _sz, _vp]),
+    "grf_cg_poly_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "grf_cg_poly_solve_f64": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _vp, _i64,
+                                     _i32, _dbl, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "grf_cg_poly_solve_lanczos_f64": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _vp,
+                                             _i64, _i32, _dbl, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp, _i64, _vp]),
+    "grf_poly_grad_workspace_bytes": (_sz, [_i64, _i32]),
+    "grf_poly_grad_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _sz,
+                                 _vp]),
 }
 
 _lib = None

@@ -208,6 +208,44 @@ class DensePlanes:
         self.P.record_stream(stream)
 
 
+class WalkPolynomial:
+    """The exact walk-power kernel's feature matrix Phi = p(G) = sum_l f_l G^l as a matrix-free operator: the
+    walk matrix ``G`` (a DeviceCSR with fp64 values, as ``GRFEngine.laplacian`` returns it, or a scipy matrix)
+    and its transpose, built once here with torch (a stable sort by column).  Nothing is assumed symmetric; for
+    a symmetric G the transpose aliases G.  A modulator f enters with its first ``min(len(f), L)`` entries, as
+    in ``StepMatrices.phi``.  ``GRFEngine.poly_apply`` / ``poly_gram_matvec`` / ``cg_solve_poly`` /
+    ``marginal_log_likelihood`` / ``pathwise_predict`` run on it; the powers of G are never formed."""
+
+    def __init__(self, G, max_walk_length: int, engine: Optional["GRFEngine"] = None):
+        if int(max_walk_length) < 1:
+            raise ValueError("WalkPolynomial: max_walk_length must be at least 1")
+        self.engine = engine or get_engine(G.ptr.device if isinstance(G, DeviceCSR) else None)
+        G = self.engine.to_device(G)
+        if G.n_rows != G.n_cols:
+            raise ValueError("WalkPolynomial: the walk matrix must be square")
+        if G.val is None:
+            raise ValueError("WalkPolynomial: the walk matrix needs float64 values")
+        self.G = G
+        self.L = int(max_walk_length)
+        self.shape = (G.n_rows, G.n_cols)
+        n, nnz = G.n_rows, G.nnz
+        cols = G.idx[:nnz].long()
+        rows = torch.repeat_interleave(torch.arange(n, device=G.ptr.device), G.ptr[1:] - G.ptr[:-1])
+        order = torch.sort(cols, stable=True)[1]  # (every column lists its rows in ascending order)
+        t_ptr = torch.zeros(n + 1, dtype=torch.int64, device=G.ptr.device)
+        t_ptr[1:] = torch.cumsum(torch.bincount(cols, minlength=n), 0)
+        t_idx = rows[order].to(torch.int32)
+        t_val = G.val[:nnz][order].contiguous()
+        if bool(torch.equal(t_ptr, G.ptr)) and bool(torch.equal(t_idx, G.idx[:nnz])) and \
+                bool(torch.equal(t_val, G.val[:nnz])):
+            self.Gt = G
+        else:
+            self.Gt = DeviceCSR(n, n, t_ptr, t_idx, t_val, None, nnz)
+
+    def n_terms(self, f) -> int:
+        return min(int(f.numel()), self.L)
+
+
 class GRFEngine:
     """All device work for one GPU.  ``device`` is a torch device (``cuda:N``)."""
 
@@ -1162,6 +1200,109 @@ class GRFEngine:
                 "grf_steps_frob_f64")
         return out
 
+    # ------------------------------------- the exact kernel as a matrix-free operator (WalkPolynomial)
+    def _poly_f(self, op: WalkPolynomial, f) -> Tuple[torch.Tensor, int]:
+        ft = torch.as_tensor(f).detach().to(self.device, torch.float64).flatten().contiguous()
+        if ft.numel() < 1:
+            raise ValueError("the modulator needs at least one entry")
+        return ft, op.n_terms(ft)
+
+    def _inv_map(self, rmap: torch.Tensor, n: int) -> torch.Tensor:
+        """node -> its position in rmap, or -1 (int32 [n]); rmap must not repeat a node."""
+        inv = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+        inv[rmap.long()] = torch.arange(rmap.numel(), dtype=torch.int32, device=self.device)
+        if int((inv >= 0).sum().item()) != rmap.numel():
+            raise ValueError("a row selection of the walk operator must not repeat a node")
+        return inv
+
+    @staticmethod
+    def _check_block(X: torch.Tensor, n_rows: int, what: str) -> None:
+        if X.dtype != torch.float64 or X.dim() != 2 or X.stride(1) != 1 or X.shape[0] != n_rows:
+            raise ValueError(f"{what} must be a float64 ({n_rows} x S) row-major matrix")
+
+    def poly_apply(self, op: WalkPolynomial, f, X: torch.Tensor, in_rows=None, out_rows=None,
+                   transpose: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Y = (p(G) S_in^T X)[out_rows] (``transpose``: p(G^T)) by Horner chains with the walk matrix
+        (grf_poly_apply_f64; fp64, S <= 256).  in_rows: the nodes X's rows belong to (None: X has a row per
+        node); out_rows: the rows wanted (None: all)."""
+        ft, n_f = self._poly_f(op, f)
+        A = op.Gt if transpose else op.G
+        n = A.n_rows
+        imap = self._row_map(in_rows)
+        self._check_block(X, n if imap is None else imap.numel(), "poly_apply: X")
+        inv = None if imap is None else self._inv_map(imap, n)
+        rmap = self._row_map(out_rows)
+        n_out = n if rmap is None else rmap.numel()
+        S = X.shape[1]
+        if out is None:
+            out = torch.empty((n_out, S), dtype=torch.float64, device=self.device)
+        ws = self._ws(self.lib.grf_poly_workspace_bytes(n, n_f, S))
+        C.check(self.lib.grf_poly_apply_f64(n, _p(A.ptr), _p(A.idx), _p(A.val), _p(ft), n_f, _p(inv), _p(rmap), n_out,
+                                            _p(X), X.stride(0), S, _p(out), out.stride(0), _p(ws), ws.numel(),
+                                            self.stream), "grf_poly_apply_f64")
+        return out
+
+    def poly_gram_matvec(self, op: WalkPolynomial, f, V: torch.Tensor, rows=None, cols=None,
+                         noise: float = 0.0) -> torch.Tensor:
+        """K[rows, cols] V = S_rows p(G) p(G)^T S_cols^T V (+ noise V when rows == cols), K never formed."""
+        W = self.poly_apply(op, f, V, in_rows=cols, transpose=True)
+        Y = self.poly_apply(op, f, W, out_rows=rows)
+        if noise:
+            Y.add_(V, alpha=float(noise))
+        return Y
+
+    def cg_solve_poly(self, op: WalkPolynomial, f, B: torch.Tensor, noise: float, rows, tolerance: float = 1.0,
+                      max_iter: int = 1000, return_residuals: bool = False, return_lanczos: bool = False):
+        """``cg_solve`` on (S_T p(G) p(G)^T S_T^T + noise I) X = B for the training nodes ``rows`` (fp64): the
+        same recurrence and return shape, every matvec two Horner chains with the walk matrix."""
+        ft, n_f = self._poly_f(op, f)
+        rmap = self._row_map(rows)
+        if rmap is None:
+            rmap = torch.arange(op.shape[0], dtype=torch.int32, device=self.device)
+        n_sys, n = rmap.numel(), op.shape[0]
+        self._check_block(B, n_sys, "cg_solve_poly: B")
+        inv = self._inv_map(rmap, n)
+        S = B.shape[1]
+        X = torch.empty((n_sys, S), dtype=torch.float64, device=self.device)
+        ws = self._ws(self.lib.grf_cg_poly_workspace_bytes(n_sys, n, S))
+        iters = ctypes.c_int32(0)
+        resid = np.zeros(S, np.float64)
+        G, Gt = op.G, op.Gt
+        head = (n_sys, n, _p(G.ptr), _p(G.idx), _p(G.val), _p(Gt.ptr), _p(Gt.idx), _p(Gt.val), _p(ft), n_f, _p(rmap),
+                _p(inv), float(noise), _p(B), B.stride(0), S, float(tolerance), int(max_iter), _p(X), X.stride(0),
+                _p(ws), ws.numel(), ctypes.byref(iters), resid.ctypes.data_as(ctypes.c_void_p))
+        coef = None
+        if return_lanczos:
+            coef = torch.empty((2 * max(int(max_iter), 0), S), dtype=torch.float64, device=self.device)
+            C.check(self.lib.grf_cg_poly_solve_lanczos_f64(*head, _p(coef), S, self.stream),
+                    "grf_cg_poly_solve_lanczos_f64")
+        else:
+            C.check(self.lib.grf_cg_poly_solve_f64(*head, self.stream), "grf_cg_poly_solve_f64")
+        return (X, int(iters.value)) + ((resid,) if return_residuals else ()) + ((coef,) if return_lanczos else ())
+
+    def poly_grad(self, op: WalkPolynomial, f, rows, A: torch.Tensor, B: torch.Tensor,
+                  wt: torch.Tensor) -> torch.Tensor:
+        """out[l] = sum_c wt[c] a_c^T (dK/df_l) b_c for K = S_T p(G) p(G)^T S_T^T, T = ``rows``, and the
+        columns a_c, b_c of A, B (len(rows) x S, fp64): (n_f,) fp64 on the device (grf_poly_grad_f64)."""
+        ft, n_f = self._poly_f(op, f)
+        rmap = self._row_map(rows)
+        n_sel, n = rmap.numel(), op.shape[0]
+        A, B = (t.to(self.device, torch.float64).contiguous() for t in (A, B))
+        self._check_block(A, n_sel, "poly_grad: A")
+        self._check_block(B, n_sel, "poly_grad: B")
+        wt = wt.to(self.device, torch.float64).flatten().contiguous()
+        S = A.shape[1]
+        if B.shape != A.shape or wt.numel() != S:
+            raise ValueError("poly_grad: A, B must be (rows x S) with one weight per column")
+        inv = self._inv_map(rmap, n)
+        out = self._empty(n_f, torch.float64)
+        ws = self._ws(self.lib.grf_poly_grad_workspace_bytes(n, S))
+        Gt = op.Gt
+        C.check(self.lib.grf_poly_grad_f64(n, _p(Gt.ptr), _p(Gt.idx), _p(Gt.val), _p(ft), n_f, n_sel, _p(inv), _p(A),
+                                           _p(B), A.stride(0), _p(wt), S, _p(out), _p(ws), ws.numel(), self.stream),
+                "grf_poly_grad_f64")
+        return out
+
     @staticmethod
     def slq_logdet(coef: np.ndarray, iters: int, sq_norms: np.ndarray) -> float:
         """Stochastic Lanczos quadrature from CG coefficients: coef (2 max_iter x t) holds the probe columns'
@@ -1195,6 +1336,8 @@ class GRFEngine:
         probes Z (n_train x t, t <= 255), log det by stochastic Lanczos quadrature from the solve's own
         coefficients, the gradients by gpytorch's estimators
             1/2 a^T dK a - 1/(2t) sum_i u_i^T dK z_i,   a = K^-1 y, u_i = K^-1 z_i.
+        ``steps``: a features.StepMatrices, or a WalkPolynomial (Phi = p(G), the exact kernel: the same
+        estimator on cg_solve_poly and poly_grad, neither Phi nor a power of G formed).
         Returns (value (float), d/df ((min(len(f), L),) fp64 device tensor), d/ds2 (float), CG iterations)."""
         tr = self._row_map(train_idx)
         n = tr.numel()
@@ -1205,9 +1348,13 @@ class GRFEngine:
         if not 1 <= t <= 255:
             raise ValueError("marginal_log_likelihood: between 1 and 255 probes per call")
         rhs = torch.cat([yv[:, None], probes.detach().to(self.device, torch.float64)], dim=1).contiguous()
-        phi = steps.phi(f)
-        phi_t = self.csr_transpose(phi, tr)
-        X, iters, coef = self.cg_solve(phi, rhs, noise, tr, phi_t, tolerance, max_iter, return_lanczos=True)
+        poly = isinstance(steps, WalkPolynomial)
+        if poly:
+            X, iters, coef = self.cg_solve_poly(steps, f, rhs, noise, tr, tolerance, max_iter, return_lanczos=True)
+        else:
+            phi = steps.phi(f)
+            phi_t = self.csr_transpose(phi, tr)
+            X, iters, coef = self.cg_solve(phi, rhs, noise, tr, phi_t, tolerance, max_iter, return_lanczos=True)
         # the weighted column sums both scalars need, one host read with the coefficients' probe columns
         wt = torch.full((1 + t,), -0.5 / t, dtype=torch.float64, device=self.device)
         wt[0] = 0.5
@@ -1219,6 +1366,8 @@ class GRFEngine:
         # d/df_l: dK = M_l[T] Phi_T^T + Phi_T M_l[T]^T; the y column pairs a with itself
         Bm = rhs
         Bm[:, 0] = X[:, 0]
+        if poly:
+            return float(value), self.poly_grad(steps, f, tr, X, Bm, wt), float(g_noise), iters
         WX = self.spmm(phi_t, X)
         WB = self.spmm(phi_t, Bm)
         n_f = min(int(f.numel()), steps.L)
@@ -1227,8 +1376,12 @@ class GRFEngine:
 
     def pathwise_predict(self, phi: DeviceCSR, train_idx, test_idx, y_train: torch.Tensor, noise: float,
                          eps1: torch.Tensor, eps2: torch.Tensor, tolerance: float = 1.0, max_iter: int = 1000,
-                         dtype: torch.dtype = torch.float64):
+                         dtype: torch.dtype = torch.float64, f=None):
         """SparseGraphGP.predict (models/sparse_grf_model.py:21-45) given its random draws.
+
+        phi: Phi as a DeviceCSR, or a WalkPolynomial with its modulator ``f`` (fp64 only): f_train and
+        f_test then come from one chain p(G) E, the solve from cg_solve_poly, and K_test,train V from
+        S_test p(G) p(G)^T S_train^T V.
 
         eps1: (S x n_nodes) prior weights, eps2: (S x n_train) noise draws (already scaled by
         the noise std).  dtype: float64 (default) or the reference's float32 for every dense
@@ -1236,6 +1389,16 @@ class GRFEngine:
         CG iteration count."""
         tr = self._row_map(train_idx)
         te = self._row_map(test_idx)
+        if isinstance(phi, WalkPolynomial):
+            if f is None or dtype != torch.float64:
+                raise ValueError("pathwise_predict: a WalkPolynomial needs its modulator f and dtype float64")
+            E = eps1.to(self.device, dtype).t().contiguous()
+            FE = self.poly_apply(phi, f, E)                                    # p(G) E: every node's prior draw
+            y = y_train.to(self.device, dtype).flatten()
+            B = y[:, None] - (FE[tr.long()] + eps2.to(self.device, dtype).t())
+            V, iters = self.cg_solve_poly(phi, f, B.contiguous(), noise, tr, tolerance, max_iter)
+            out = FE[te.long()] + self.poly_gram_matvec(phi, f, V, rows=te, cols=tr)
+            return out.t(), iters
         E = eps1.to(self.device, dtype).t().contiguous()                      # n_nodes x S
         f_train = self.spmm(phi, E, tr)                                        # (eps1 @ phi_train.T)^T
         f_test = self.spmm(phi, E, te)

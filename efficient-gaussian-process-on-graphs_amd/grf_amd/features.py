@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib as C
-from .engine import DeviceCSR, GRFEngine, _p, cols_band_width, get_engine
+from .engine import DeviceCSR, GRFEngine, WalkPolynomial, _p, cols_band_width, get_engine  # noqa: F401
 
 
 def _torch_csr(mat) -> torch.Tensor:
@@ -259,11 +259,12 @@ def grf_kernel(f: torch.Tensor, steps: StepMatrices, x1=None, x2=None, diag: boo
 class GRFMarginalLikelihoodFunction(torch.autograd.Function):
     """The matrix-free marginal log-likelihood of y under K^ = Phi(f)[T] Phi(f)[T]^T + noise I
     (``GRFEngine.marginal_log_likelihood``: CG + stochastic Lanczos quadrature, fp64, K never formed),
-    differentiable w.r.t. the modulator f and the noise.  The forward computes the value and both
+    differentiable w.r.t. the modulator f and the noise.  ``steps`` is a StepMatrices or a WalkPolynomial (the
+    exact kernel Phi = p(G) as a matrix-free operator: the same estimator, no step matrix).  The forward computes the value and both
     gradients (they share the one CG solve); the backward scales them by the incoming scalar."""
 
     @staticmethod
-    def forward(ctx, f: torch.Tensor, noise: torch.Tensor, steps: StepMatrices, train_idx, y, probes,
+    def forward(ctx, f: torch.Tensor, noise: torch.Tensor, steps, train_idx, y, probes,
                 tolerance: float, max_iter: int, info: Optional[dict]):
         eng = steps.engine
         value, g_f, g_noise, iters = eng.marginal_log_likelihood(
@@ -295,11 +296,12 @@ def resolve_cg_tolerance(tolerance: Optional[float]) -> float:
     return float(gpytorch.settings.cg_tolerance.value())
 
 
-def grf_marginal_log_likelihood(f: torch.Tensor, noise, steps: StepMatrices, train_idx, y, probes=None,
+def grf_marginal_log_likelihood(f: torch.Tensor, noise, steps, train_idx, y, probes=None,
                                 n_probes: int = 64, generator=None, tolerance: Optional[float] = None,
                                 max_iter: int = 1000, per_datum: bool = True,
                                 info: Optional[dict] = None) -> torch.Tensor:
-    """MLL(f, noise) of y at the training nodes, a differentiable fp64 scalar (on f's device).
+    """MLL(f, noise) of y at the training nodes, a differentiable fp64 scalar (on f's device).  steps: a
+    StepMatrices (Phi = sum_l f_l M_l) or a WalkPolynomial (Phi = sum_l f_l G^l, matrix-free).
 
     f, noise: torch tensors (noise with one element; a float is a constant) -- the gradient flows to
     whatever they were computed from.  probes: (n_train x t) Hutchinson probes, t <= 255; by default

@@ -677,6 +677,76 @@ int32_t grf_spgemm_csr_fill(int64_t n_rows, int64_t n_mid, int64_t n_cols, const
                             const int64_t *c_ptr, int32_t *c_idx, double *c_val, float *c_val32, void *workspace,
                             size_t workspace_bytes, grf_stream_t stream);
 
+/* ------------------------------------------- the exact walk-power kernel as a matrix-free operator
+ * Phi = p(G) = sum_{l < n_f} f_l G^l (the exact kernel of general_kernel_pofm.py:7-42, :45-96) without its
+ * powers, which fill in (G^4 of a mean-degree-20 graph is dense): every product is a Horner chain with the
+ * walk matrix itself,
+ *     H_{n_f-1} = f_{n_f-1} X,   H_l = A H_{l+1} + f_l X  (l = n_f - 2 .. 0),   p(A) X = H_0,
+ * and K_TT V = S_T p(G) p(G)^T S_T^T V is two chains, one with G^T and one with G.  A: n x n CSR as
+ * grf_laplacian_csr writes it (int64 row pointers, sorted int32 columns, float64 values); it is NOT assumed
+ * symmetric, the caller passes G^T where the transpose is meant.  f: n_f >= 1 coefficients on the DEVICE.
+ * Dense blocks are float64 row-major with the n_rhs in [1, 256] right-hand sides as columns.
+ *
+ * Order rule.  One output element of a step is computed as follows (fp64 throughout):
+ *   1. start from +0.0;
+ *   2. add the row's products val[e] * x[idx[e], c] one at a time in the order of the row's entries
+ *      (ascending column), each by one fused multiply-add; in the chain's first step the gathered value is
+ *      x = RN(f_{n_f-1} * X[., c]) (the scale of H_{n_f-1} folded into the read);
+ *   3. add the f_l X addend by one fused multiply-add, fma(f_l, X[row, c], sum);
+ *   4. add the noise addend, if present, by one fused multiply-add, fma(noise, P[r, c], sum).
+ * n_f = 1 is the single step 0.0 + f_0 X without a matrix (K_TT = f_0^2 I).  Rows that a map sends to -1
+ * add nothing in steps 2 and 3.  No floating-point atomics: two calls give the same bits. */
+
+/* Y = p(A) X~ on the rows `row_map` (general_kernel_pofm.py:45-96: the kernel's products without K).
+ * inv_map (int32 [n], optional): node -> its row of X, or -1 for a node whose row of X~ is zero (X~ = S^T X
+ * for a node subset, never stored); NULL: X has n rows.  row_map (int32 [n_out], optional): the rows of p(A) X~
+ * written to Y (n_out x ldy); NULL: all of them, and n_out must be n.  ldx, ldy >= n_rhs; nothing outside
+ * [rows x n_rhs] of Y is written.  Y and the workspace must not overlap X.  Workspace:
+ * grf_poly_workspace_bytes(n, n_f, n_rhs) bytes (two n x n_rhs blocks; none for n_f <= 2). */
+size_t grf_poly_workspace_bytes(int64_t n, int32_t n_f, int32_t n_rhs);
+int32_t grf_poly_apply_f64(int64_t n, const int64_t *ptr, const int32_t *idx, const double *val, const double *f,
+                           int32_t n_f, const int32_t *inv_map, const int32_t *row_map, int64_t n_out,
+                           const double *X, int64_t ldx, int32_t n_rhs, double *Y, int64_t ldy, void *workspace,
+                           size_t workspace_bytes, grf_stream_t stream);
+
+/* grf_cg_gram_solve_f64 / grf_cg_gram_solve_lanczos_f64 (same contract, same recurrence, reductions, stopping
+ * rule, polling and coefficient records) on A = S_T p(G) p(G)^T S_T^T + noise I: models/sparse_grf_model.py:21-45
+ * on the exact kernel.  (g_*, gt_*): G and G^T (n x n); row_map (int32 [n_sys]): the training nodes T;
+ * inv_map (int32 [n]): a node's position in row_map, or -1.  Every matvec is the chain with G^T read from the
+ * direction block through inv_map, then the chain with G whose last step runs on row_map only and adds
+ * noise * P.  Workspace: grf_cg_poly_workspace_bytes(n_sys, n, n_rhs). */
+size_t grf_cg_poly_workspace_bytes(int64_t n_sys, int64_t n, int32_t n_rhs);
+int32_t grf_cg_poly_solve_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                              const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
+                              const double *f, int32_t n_f, const int32_t *row_map, const int32_t *inv_map,
+                              double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs, double tolerance,
+                              int32_t max_iter, double *x, int64_t ldx, void *workspace, size_t workspace_bytes,
+                              int32_t *iters_out, double *resid_out, grf_stream_t stream);
+int32_t grf_cg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                                      const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
+                                      const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
+                                      const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs,
+                                      int32_t n_rhs, double tolerance, int32_t max_iter, double *x, int64_t ldx,
+                                      void *workspace, size_t workspace_bytes, int32_t *iters_out, double *resid_out,
+                                      double *coef, int64_t ld_coef, grf_stream_t stream);
+
+/* The modulator gradient's contraction on the operator (the training step of models/sparse_grf_model.py:21-45's
+ * model; A, B, wt as in grf_steps_frob_f64): with a~ = S_T^T A, b~ = S_T^T B, W_A = p(G^T) a~, W_B = p(G^T) b~,
+ * U_l = (G^T)^l a~, V_l = (G^T)^l b~,
+ *     out[l] = sum_c wt[c] ( <U_l[:, c], W_B[:, c]> + <V_l[:, c], W_A[:, c]> ),  l < n_f,
+ * which is sum_c wt[c] a_c^T (dK^/df_l) b_c.  A, B: n_sel x ld (ld >= n_rhs); inv_map (int32 [n]): a node's row
+ * of A / B, or -1.  Each step U_l = G^T U_{l-1} is fused with its inner products; per element of U_l the
+ * order rule's steps 1-2, then per node fma(wt[c], fma(U, W_B, RN(V W_A)), sum) over the node's columns
+ * c = lane, lane + 64, ...; a wave's nodes ascending, the 64 lanes by an xor tree, the 4 waves in order, one
+ * fp64 partial per block, the last block (by a ticket at the workspace's start, zero again afterwards) adds
+ * the partials in block order.  out: n_f doubles on the device.  Workspace:
+ * grf_poly_grad_workspace_bytes(n, n_rhs) (six n x n_rhs blocks). */
+size_t grf_poly_grad_workspace_bytes(int64_t n, int32_t n_rhs);
+int32_t grf_poly_grad_f64(int64_t n, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
+                          const double *f, int32_t n_f, int64_t n_sel, const int32_t *inv_map, const double *A,
+                          const double *B, int64_t ld, const double *wt, int32_t n_rhs, double *out, void *workspace,
+                          size_t workspace_bytes, grf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
