@@ -17,6 +17,15 @@
 // that miss L2; the symmetric mode computes the tiles on and above the diagonal
 // band and a mirror pass copies the upper triangle down.
 //
+// Structure: two kernels produce every sparse K -- gram_sparse_kernel (a tile per workgroup; line, packed and slot
+// buckets) and gram_slot_pipe_kernel (persistent, software-pipelined over its tiles; slot buckets, column blocks).
+// They differ in how a wave's nonzeros and bucket descriptors reach its registers; from there both run the same
+// code, each piece written once: slot_buckets (a slot header's two virtual buckets), gram_stream_batch (scans,
+// bucket ids by gram_propagate_ids, window groups by gram_windows, the exact tail group) on a GramWaveState, and
+// gram_tile_out (the write-out).  On the host the entry points fill one GramArgs, checked by gram_check and run by
+// gram_tiles_launch (one loop over launches of at most 2^32 work-items).  GRF_GRAM_PIPE is the one environment
+// variable read here; the measured-and-decided choices (waves per tile, the split, the shares) are plain rules.
+//
 // Dense path: grf_gram_dense.hip (fp32 MFMA, 128 x 128 tiles on and above the diagonal).
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,6 +51,11 @@ typedef uint32_t uint4_v __attribute__((ext_vector_type(4)));
 #else
 #define GRF_K_STORE(v, p) (*(p) = (v))
 #define GRF_K_LOAD(p) (*(p))
+#endif
+// -DGRF_GRAM_PIPE_ABLATE=1 / 2: timing-only builds of the pipelined column-block kernel without its gathers /
+// without its K stores (K is wrong: never the library a result comes from; profiles/r06_c5_gram_ab.txt)
+#ifndef GRF_GRAM_PIPE_ABLATE
+#define GRF_GRAM_PIPE_ABLATE 0
 #endif
 
 constexpr int kChunk = 1024;  // stream positions covered by one bucket-id chunk (16 per lane)
@@ -82,18 +96,33 @@ __device__ inline int wave_incl_max(int v) {
     return v;
 }
 
-// Bucket ids of a chunk of 1024 stream positions from bucket-start markers: bid[p] holds
-// (bucket + 1) at the first position of every non-empty bucket and 0 elsewhere; since the
-// ids increase along the stream, the id of a position is the running maximum.  Lane l owns
-// positions 16 l .. 16 l + 15 (one 16-byte LDS read and write); carry = the id running at
-// the chunk start (0 for the first chunk).  Returns the id running at the chunk end.
+// Bucket ids of a chunk of 64 * 4 * NW stream positions (NW = 1, 2, 4: 256, 512, 1024) from bucket-start
+// markers: bid[p] holds (bucket + 1) at the first position of every non-empty bucket and 0 elsewhere; since the
+// ids increase along the stream, the id of a position is the running maximum.  Lane l owns positions
+// 4 NW l .. 4 NW l + 4 NW - 1 (one LDS read and write of 4 NW bytes); carry = the id running at the chunk start
+// (0 for the first chunk).  Returns the id running at the chunk end.  A short stream (C5's column-block tiles:
+// ~235 pairs per wave) pays for the positions it has instead of 1024 (NW = 4 is ~110 VALU per lane and batch).
+template <int NW>
 __device__ inline int gram_propagate_ids(unsigned char *bid, int carry, int lane) {
-    uint4 x = reinterpret_cast<uint4 *>(bid)[lane];
-    uint32_t w[4] = {x.x, x.y, x.z, x.w};
-    // in-lane running max over the 16 bytes (from 0), and the lane's maximum
+    static_assert(NW == 1 || NW == 2 || NW == 4, "one 4-, 8- or 16-byte LDS access per lane");
+    uint32_t w[NW];
+    if constexpr (NW == 1) {
+        w[0] = reinterpret_cast<uint32_t *>(bid)[lane];
+    } else if constexpr (NW == 2) {
+        const uint2 x = reinterpret_cast<uint2 *>(bid)[lane];
+        w[0] = x.x;
+        w[1] = x.y;
+    } else {
+        const uint4 x = reinterpret_cast<uint4 *>(bid)[lane];
+        w[0] = x.x;
+        w[1] = x.y;
+        w[2] = x.z;
+        w[3] = x.w;
+    }
+    // in-lane running max over the bytes (from 0), and the lane's maximum
     int run = 0;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NW; ++i) {
         uint32_t o = 0;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -105,9 +134,8 @@ __device__ inline int gram_propagate_ids(unsigned char *bid, int carry, int lane
     // ids running into this lane: the maximum over the previous lanes and the carry
     int before = __builtin_amdgcn_update_dpp(0, wave_incl_max(run), 0x138, 0xf, 0xf, false);  // wave_shr:1
     before = max(before, carry);
-    const uint32_t rep = (uint32_t)before * 0x01010101u;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NW; ++i) {
         // bytewise max(w, before): the bytes of w are non-decreasing, so only a leading run
         // of bytes below `before` changes
         uint32_t o = 0;
@@ -118,58 +146,28 @@ __device__ inline int gram_propagate_ids(unsigned char *bid, int carry, int lane
         }
         w[i] = o;
     }
-    (void)rep;
-    reinterpret_cast<uint4 *>(bid)[lane] = make_uint4(w[0], w[1], w[2], w[3]);
-    return __builtin_amdgcn_readlane(max(run, before), 63);
-}
-
-// gram_propagate_ids over a chunk of 64 * 4 * NW positions (NW = 1, 2: 4 or 8 per lane, one LDS read and write
-// of 4 NW bytes): a short stream (C5's column-block tiles: ~235 pairs per wave) pays for the positions it has
-// instead of 1024 (the 16-byte form is ~110 VALU per lane and batch)
-template <int NW>
-__device__ inline int gram_propagate_ids_n(unsigned char *bid, int carry, int lane) {
-    uint32_t w[NW];
-    if constexpr (NW == 1) {
-        w[0] = reinterpret_cast<uint32_t *>(bid)[lane];
-    } else {
-        const uint2 x = reinterpret_cast<uint2 *>(bid)[lane];
-        w[0] = x.x;
-        w[1] = x.y;
-    }
-    int run = 0;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        uint32_t o = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            run = max(run, (int)((w[i] >> (8 * b)) & 0xffu));
-            o |= (uint32_t)run << (8 * b);
-        }
-        w[i] = o;
-    }
-    int before = __builtin_amdgcn_update_dpp(0, wave_incl_max(run), 0x138, 0xf, 0xf, false);  // wave_shr:1
-    before = max(before, carry);
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        uint32_t o = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const uint32_t v = (w[i] >> (8 * b)) & 0xffu;
-            o |= (v > (uint32_t)before ? v : (uint32_t)before) << (8 * b);
-        }
-        w[i] = o;
-    }
     if constexpr (NW == 1) reinterpret_cast<uint32_t *>(bid)[lane] = w[0];
-    else reinterpret_cast<uint2 *>(bid)[lane] = make_uint2(w[0], w[1]);
+    else if constexpr (NW == 2) reinterpret_cast<uint2 *>(bid)[lane] = make_uint2(w[0], w[1]);
+    else reinterpret_cast<uint4 *>(bid)[lane] = make_uint4(w[0], w[1], w[2], w[3]);
     return __builtin_amdgcn_readlane(max(run, before), 63);
 }
 
-// Per-wave state of one flattened batch stream (see gram_sparse_kernel).
+// A wave's LDS state of one flattened batch stream, behind the workgroup's W accumulators.
+struct GramWaveState {
+    unsigned char *bid;  // [kChunk] bucket of every stream position of the current chunk
+    int32_t *tbase;      // [64 kV] per bucket: byte offset of its first pair (from the band's first line)
+                         // - 12 * stream position
+    float *aval;         // [64 kV] per bucket: Phi[row,k]
+};
+
+__device__ inline GramWaveState gram_wave_state(unsigned long long *acc, int64_t W, int wave, int kV) {
+    unsigned char *st = reinterpret_cast<unsigned char *>(acc + W) + wave * wave_state_bytes(kV);
+    return {st, reinterpret_cast<int32_t *>(st + kChunk), reinterpret_cast<float *>(st + kChunk + 64 * kV * 4)};
+}
+
+// What the windows of one tile's streams read and add to (see gram_sparse_kernel).
 struct GramStream {
-    const unsigned char *bid;   // bucket of every stream position of the current chunk (LDS)
-    const int32_t *tbase;       // per bucket: byte offset of its first pair (from the band's
-                                // first line) - 12 * stream position (LDS)
-    const float *aval;          // per bucket: Phi[row,k] (LDS)
+    GramWaveState st;           // the wave's bucket ids and per-bucket bases and values (LDS)
     __amdgpu_buffer_rsrc_t rec; // the band's record pairs, 12 bytes each (global, 32-bit offsets)
     unsigned char *acc;         // tile accumulator (LDS), addressed by byte offset
     double S;                   // the row's fixed-point scale 2^sh
@@ -183,33 +181,28 @@ struct __attribute__((aligned(4))) RecPair {
 };
 
 // NW windows of 64 pairs starting at stream position w0 (chunk base c0, chunk end cend).
-// TAIL: positions >= cend are masked (they read pair 0 of the band and add exactly 0 to distinct
-// entries) -- 0: no window, 1: the last window only (an exact tail group: NW = ceil((cend - w0) / 64),
-// so every other window is full), 2: every window.
+// TAIL = 1: an exact tail group, NW = ceil((cend - w0) / 64) -- every window is full but the last, whose
+// positions >= cend are masked (they read a finite pair and add exactly 0 to distinct entries); 0: all full.
 template <int NW, int TAIL>
 __device__ __forceinline__ void gram_windows(const GramStream &g, int32_t w0, int32_t c0, int32_t cend, int lane) {
+    static_assert(TAIL == 0 || TAIL == 1, "only the last window of a group is ever masked");
+    const bool last_ok = !TAIL || w0 + (NW - 1) * 64 + lane < cend;
     int m[NW];
 #pragma unroll
     for (int u = 0; u < NW; ++u) {
         const int32_t p = w0 + u * 64 + lane;
-        const bool mk = TAIL == 2 || (TAIL == 1 && u == NW - 1);  // (compile-time per window)
-        m[u] = (!mk || p < cend) ? (int)g.bid[p - c0] - 1 : 0;
+        m[u] = (u != NW - 1 || last_ok) ? (int)g.st.bid[p - c0] - 1 : 0;
     }
     int32_t pos[NW];
     double sc[NW];
 #pragma unroll
     for (int u = 0; u < NW; ++u) {
-        pos[u] = g.tbase[m[u]] + 12 * (w0 + u * 64 + lane);
-        sc[u] = (double)g.aval[m[u]] * g.S;  // exact: a power-of-two scaling of an f32
+        pos[u] = g.st.tbase[m[u]] + 12 * (w0 + u * 64 + lane);
+        sc[u] = (double)g.st.aval[m[u]] * g.S;  // exact: a power-of-two scaling of an f32
     }
     if (TAIL) {
-#pragma unroll
-        for (int u = 0; u < NW; ++u) {
-            if (TAIL == 1 && u != NW - 1) continue;
-            const bool ok = w0 + u * 64 + lane < cend;
-            pos[u] = ok ? pos[u] : g.safe;  // the band's first pair (slots: slot 0's first pair): finite
-            sc[u] = ok ? sc[u] : 0.0;
-        }
+        pos[NW - 1] = last_ok ? pos[NW - 1] : g.safe;  // the band's first pair (slots: slot 0's first pair): finite
+        sc[NW - 1] = last_ok ? sc[NW - 1] : 0.0;
     }
     // phase order pinned: all descriptor reads, then all gathers in flight, then the adds
     __builtin_amdgcn_sched_barrier(0);
@@ -227,10 +220,9 @@ __device__ __forceinline__ void gram_windows(const GramStream &g, int32_t w0, in
         const long long q0 = fx_fma_round(sc[u], (double)rec[u].v0);
         const long long q1 = fx_fma_round(sc[u], (double)rec[u].v1);
         uint32_t c0 = rec[u].cols & 0xffffu, c1 = rec[u].cols >> 16;
-        if (TAIL == 2 || (TAIL == 1 && u == NW - 1)) {
-            const bool ok = w0 + u * 64 + lane < cend;
-            c0 = ok ? c0 : (uint32_t)(lane & 15) * 8u;
-            c1 = ok ? c1 : (uint32_t)(lane & 15) * 8u;
+        if (TAIL && u == NW - 1) {
+            c0 = last_ok ? c0 : (uint32_t)(lane & 15) * 8u;
+            c1 = last_ok ? c1 : (uint32_t)(lane & 15) * 8u;
         }
         __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(g.acc + c0), (unsigned long long)q0,
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -248,6 +240,124 @@ __device__ inline float fx_to_float(unsigned long long a, int sh) {
     const int lo = (int)(unsigned)(a & 0xffffffffull);
     const int hi = (int)(a >> 32) - (lo >> 31);
     return ldexpf(fmaf((float)hi, 4294967296.0f, (float)lo), -sh);
+}
+
+// The two virtual buckets of a GRF_REC_SLOT slot (header d = {pairs, first overflow pair} at byte sb of t_rec, a
+// slot without a nonzero passed as {0, 0}): the first two pairs lie in the slot behind the header, the others
+// behind all slots at ovf_base + 12 d.y.
+__device__ __forceinline__ void slot_buckets(uint2 d, int32_t sb, int32_t ovf_base, int32_t *t0, int32_t *cnt) {
+    const int32_t inl = min((int32_t)d.x, 2);
+    t0[0] = sb + 8;
+    cnt[0] = inl;
+    t0[1] = ovf_base + kPairBytesG * (int32_t)d.y;
+    cnt[1] = (int32_t)d.x - inl;
+}
+
+constexpr int kGramUnroll = 8;  // windows of gathers in flight per wave (4 and 16 measured slower: AB_LOG rounds 1..3)
+
+// One batch of a wave: lane l holds the buckets h * 64 + l (h < kV) -- cnt pairs from byte t0 of the band's
+// records, times av = Phi[row, k] -- already in registers.  The buckets are flattened into one stream of pairs
+// (a scan of the counts), the bucket of every stream position comes from a u8 id per position (bucket-start
+// markers propagated by a running maximum, in chunks of 256 / 512 / 1024 positions: the propagation's VALU scales
+// with the chunk), and the stream is gathered and added in groups of kGramUnroll windows of 64 pairs, the last
+// group with exactly the windows left (a full group would issue up to kGramUnroll - 1 all-masked windows of loads
+// and LDS adds per batch).
+template <int kV>
+__device__ __forceinline__ void gram_stream_batch(const GramStream &gs, const int32_t *cnt, const int32_t *t0,
+                                                  const float *av, int lane) {
+    const GramWaveState &st = gs.st;
+    int32_t excl[kV];
+    int32_t total = 0;
+#pragma unroll
+    for (int h = 0; h < kV; ++h) {
+        const int32_t inc = wave_inclusive_scan<int32_t>(cnt[h]) + total;  // (DPP: grf_block.h)
+        excl[h] = inc - cnt[h];
+        total = __builtin_amdgcn_readlane(inc, 63);
+    }
+#pragma unroll
+    for (int h = 0; h < kV; ++h) {
+        st.tbase[h * 64 + lane] = t0[h] - 12 * excl[h];  // byte offset = tbase + 12 * position
+        st.aval[h * 64 + lane] = av[h];
+    }
+    int carry = 0;
+    const int32_t chunk = total <= 256 ? 256 : total <= 512 ? 512 : kChunk;
+    for (int32_t c0 = 0; c0 < total; c0 += chunk) {
+        const int32_t cend = (total - c0) < chunk ? total : c0 + chunk;
+        // bucket ids of the chunk: clear, mark every non-empty bucket's first position, propagate
+        if (chunk == 256) reinterpret_cast<uint32_t *>(st.bid)[lane] = 0u;
+        else if (chunk == 512) reinterpret_cast<uint2 *>(st.bid)[lane] = make_uint2(0u, 0u);
+        else reinterpret_cast<uint4 *>(st.bid)[lane] = make_uint4(0u, 0u, 0u, 0u);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int h = 0; h < kV; ++h)
+            if (cnt[h] > 0 && excl[h] >= c0 && excl[h] < cend)
+                st.bid[excl[h] - c0] = (unsigned char)(h * 64 + lane + 1);
+        __builtin_amdgcn_wave_barrier();
+        carry = chunk == 256   ? gram_propagate_ids<1>(st.bid, carry, lane)
+                : chunk == 512 ? gram_propagate_ids<2>(st.bid, carry, lane)
+                               : gram_propagate_ids<4>(st.bid, carry, lane);
+        __builtin_amdgcn_wave_barrier();
+        int32_t w0 = c0;
+        for (; w0 + 64 * kGramUnroll <= cend; w0 += 64 * kGramUnroll)
+            gram_windows<kGramUnroll, 0>(gs, w0, c0, cend, lane);
+        if (w0 < cend) {
+            static_assert(kGramUnroll == 8, "the tail switch lists 1 .. 8 windows");
+            switch ((cend - w0 + 63) >> 6) {
+                case 1: gram_windows<1, 1>(gs, w0, c0, cend, lane); break;
+                case 2: gram_windows<2, 1>(gs, w0, c0, cend, lane); break;
+                case 3: gram_windows<3, 1>(gs, w0, c0, cend, lane); break;
+                case 4: gram_windows<4, 1>(gs, w0, c0, cend, lane); break;
+                case 5: gram_windows<5, 1>(gs, w0, c0, cend, lane); break;
+                case 6: gram_windows<6, 1>(gs, w0, c0, cend, lane); break;
+                case 7: gram_windows<7, 1>(gs, w0, c0, cend, lane); break;
+                default: gram_windows<8, 1>(gs, w0, c0, cend, lane); break;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+
+// A finished tile out to krow[c_lo, wlen) (krow = &K[r, j0]; non-temporal: K is write-once), converted from the
+// fixed-point sums of shift sh: 16-byte stores when the row and j0 allow them, with a scalar tail, else scalar
+// stores from c_lo (a multiple of 8: a diagonal tile's sub-band, whose earlier columns hold partial sums).
+// addk: K already holds the dense hub-column part of these entries, and the sum is rounded once and added to it.
+// kZero: every accumulator written out is zeroed for the workgroup's next tile (the persistent kernel, c_lo = 0).
+template <bool kZero>
+__device__ __forceinline__ void gram_tile_out(unsigned long long *acc, float *krow, bool vec, int64_t c_lo,
+                                              int64_t wlen, int sh, bool addk, int tid, int threads) {
+#if GRF_GRAM_PIPE_ABLATE == 2
+    constexpr bool store = !kZero;  // (timing-only build of the persistent kernel without its K stores: wrong K)
+#else
+    constexpr bool store = true;
+#endif
+    u64x2 *acc2 = reinterpret_cast<u64x2 *>(acc);
+    const u64x2 z2 = {0ull, 0ull};
+    int64_t done = c_lo;
+    if (vec) {
+        const int64_t n4 = wlen / 4;
+        f32x4 *k4 = reinterpret_cast<f32x4 *>(krow);
+        for (int64_t i = c_lo / 4 + tid; i < n4; i += threads) {
+            const u64x2 a = acc2[2 * i], b = acc2[2 * i + 1];
+            f32x4 o;
+            o[0] = fx_to_float(a[0], sh);
+            o[1] = fx_to_float(a[1], sh);
+            o[2] = fx_to_float(b[0], sh);
+            o[3] = fx_to_float(b[1], sh);
+            if (addk) o += __builtin_nontemporal_load(&k4[i]);
+            if (store) GRF_K_STORE(o, &k4[i]);
+            if (kZero) {
+                acc2[2 * i] = z2;
+                acc2[2 * i + 1] = z2;
+            }
+        }
+        done = n4 * 4;
+    }
+    for (int64_t i = done + tid; i < wlen; i += threads) {
+        if (store) krow[i] = addk ? fx_to_float(acc[i], sh) + krow[i] : fx_to_float(acc[i], sh);
+        if (kZero) acc[i] = 0ull;
+    }
 }
 
 // LDS bytes of one gram_sparse_kernel workgroup (W int64 counters + per-wave stream state):
@@ -301,13 +411,13 @@ struct GramTiles {
 // batches w, w + kWaves, ... of 128 nonzeros of the row and flattens each batch's buckets
 // into one stream of PAIRS.  The bucket of each pair comes from a per-position u8 bucket
 // id (bucket-start markers propagated by a running maximum, one LDS read); the gathers of kGramUnroll
-// windows of 64 pairs are in flight together.  Tiles are dispatched band-major, so the
-// tiles in flight share one band's records (L2 / Infinity Cache).
+// windows of 64 pairs are in flight together (gram_stream_batch, shared with the pipelined kernel below).
+// Tiles are dispatched band-major, so the tiles in flight share one band's records (L2 / Infinity Cache).
 // kSlot: the transpose is in the GRF_REC_SLOT layout -- bucket b's header {pairs, first overflow pair}
 // and its first two pairs in the 32-byte slot t_rec + 32 b, the other pairs at t_rec + ovf_base + 12 p --
 // so every nonzero contributes two virtual buckets (inline part, overflow part) to the wave's stream,
 // and a small bucket costs one line (header and pairs) instead of a descriptor line and a record line.
-template <int kWaves, int kHalves, int kGramUnroll, bool kTailExact, bool kSlot = false>
+template <int kWaves, int kHalves, bool kSlot>
 __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
     int64_t n_total, int64_t row_begin, GramTiles tl, int64_t t_begin, const int64_t *__restrict__ ptr,
     const int32_t *__restrict__ idx, const float *__restrict__ val, const uint2 *__restrict__ t_desc,
@@ -320,10 +430,6 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
     const int64_t W = tl.W;
     constexpr int kB = 64 * kHalves;        // nonzeros per wave batch
     constexpr int kV = kSlot ? 2 * kHalves : kHalves;  // stream buckets per lane and batch
-    unsigned char *st = reinterpret_cast<unsigned char *>(acc + W) + wave * wave_state_bytes(kV);
-    unsigned char *bidv = st;                                          // [kChunk]
-    int32_t *tbase = reinterpret_cast<int32_t *>(st + kChunk);         // [64 kV]
-    float *aval = reinterpret_cast<float *>(st + kChunk + 64 * kV * 4);  // [64 kV]
 
     int64_t J, r;
     tl.locate(t_begin + (int64_t)blockIdx.x, J, r);
@@ -344,14 +450,13 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
     // starts at that sub-band's first column
     const int dsub = (t_split && tl.sym && r >= J_local * W) ? (int)(((r - J_local * W) * kSub) / W) : 0;
 
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     u64x2 *acc2 = reinterpret_cast<u64x2 *>(acc);
     const u64x2 z2 = {0ull, 0ull};
     for (int64_t i = tid; i < W / 2; i += 64 * kWaves) acc2[i] = z2;
     if (kWaves > 1) __syncthreads();
     else __builtin_amdgcn_wave_barrier();
 
-    const GramStream gs{bidv, tbase, aval,
+    const GramStream gs{gram_wave_state(acc, W, wave, kV),
                         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(brec), (short)0, 0x7fffffff,
                                                           0x00020000),
                         reinterpret_cast<unsigned char *>(acc), ldexp(1.0, sh), kSlot ? 8 : 0};
@@ -372,7 +477,7 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
     const int64_t gstep = (balance || row_cuts) ? kB : (int64_t)kB * kWaves;
     for (int64_t g0 = ws0; g0 < ws1; g0 += gstep) {
         const int64_t gend = (balance || row_cuts) ? ((g0 + kB) < ws1 ? g0 + kB : ws1) : e1;
-        int32_t cnt[kV], excl[kV], t0[kV];
+        int32_t cnt[kV], t0[kV];
         float av[kV];
 #pragma unroll
         for (int h = 0; h < kHalves; ++h) {
@@ -384,11 +489,7 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
                 // the slot's header and inline pairs share its line; the overflow pairs follow all slots
                 const int64_t sb = 32 * (boff + (k >= 0 ? k : 0));
                 const uint2 d = k >= 0 ? *reinterpret_cast<const uint2 *>(t_rec + sb) : make_uint2(0u, 0u);
-                const int32_t inl = min((int32_t)d.x, 2);
-                t0[2 * h] = (int32_t)sb + 8;
-                cnt[2 * h] = inl;
-                t0[2 * h + 1] = (int32_t)ovf_base + kPairBytesG * (int32_t)d.y;
-                cnt[2 * h + 1] = (int32_t)d.x - inl;
+                slot_buckets(d, (int32_t)sb, (int32_t)ovf_base, &t0[2 * h], &cnt[2 * h]);
                 av[2 * h] = a;
                 av[2 * h + 1] = a;
             } else {
@@ -400,90 +501,14 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
                 cnt[h] = (int32_t)d.y - skip;                                   // pairs
             }
         }
-        int32_t total = 0;
-#pragma unroll
-        for (int h = 0; h < kV; ++h) {
-            const int32_t inc = wave_inclusive_scan<int32_t>(cnt[h]) + total;  // (DPP: grf_block.h)
-            excl[h] = inc - cnt[h];
-            total = __builtin_amdgcn_readlane(inc, 63);
-        }
-#pragma unroll
-        for (int h = 0; h < kV; ++h) {
-            tbase[h * 64 + lane] = t0[h] - 12 * excl[h];  // byte offset = tbase + 12 * position
-            aval[h * 64 + lane] = av[h];
-        }
-        int carry = 0;
-        // (chunks of 256 / 512 positions when the stream is that short: the propagation's VALU scales with it)
-        const int32_t chunk = total <= 256 ? 256 : total <= 512 ? 512 : kChunk;
-        for (int32_t c0 = 0; c0 < total; c0 += chunk) {
-            const int32_t cend = (total - c0) < chunk ? total : c0 + chunk;
-            // bucket ids of the chunk: clear, mark every non-empty bucket's first position, propagate
-            if (chunk == 256) reinterpret_cast<uint32_t *>(bidv)[lane] = 0u;
-            else if (chunk == 512) reinterpret_cast<uint2 *>(bidv)[lane] = make_uint2(0u, 0u);
-            else reinterpret_cast<uint4 *>(bidv)[lane] = make_uint4(0u, 0u, 0u, 0u);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int h = 0; h < kV; ++h)
-                if (cnt[h] > 0 && excl[h] >= c0 && excl[h] < cend)
-                    bidv[excl[h] - c0] = (unsigned char)(h * 64 + lane + 1);
-            __builtin_amdgcn_wave_barrier();
-            carry = chunk == 256   ? gram_propagate_ids_n<1>(bidv, carry, lane)
-                    : chunk == 512 ? gram_propagate_ids_n<2>(bidv, carry, lane)
-                                   : gram_propagate_ids(bidv, carry, lane);
-            __builtin_amdgcn_wave_barrier();
-            int32_t w0 = c0;
-            for (; w0 + 64 * kGramUnroll <= cend; w0 += 64 * kGramUnroll)
-                gram_windows<kGramUnroll, 0>(gs, w0, c0, cend, lane);
-            if (w0 < cend) {
-                // last group: exactly the windows left (a group of kGramUnroll would issue up to
-                // kGramUnroll - 1 all-masked windows of loads and LDS adds per batch)
-                if (kTailExact) {
-                    switch ((cend - w0 + 63) >> 6) {
-                        case 1: gram_windows<1, 1>(gs, w0, c0, cend, lane); break;
-                        case 2: gram_windows<2, 1>(gs, w0, c0, cend, lane); break;
-                        case 3: gram_windows<3, 1>(gs, w0, c0, cend, lane); break;
-                        case 4: gram_windows<4, 1>(gs, w0, c0, cend, lane); break;
-                        case 5: gram_windows<kGramUnroll < 5 ? kGramUnroll : 5, 1>(gs, w0, c0, cend, lane); break;
-                        case 6: gram_windows<kGramUnroll < 6 ? kGramUnroll : 6, 1>(gs, w0, c0, cend, lane); break;
-                        case 7: gram_windows<kGramUnroll < 7 ? kGramUnroll : 7, 1>(gs, w0, c0, cend, lane); break;
-                        // (unroll <= 8: exactly kGramUnroll windows are left here; 16: 8 .. 16 are, so every window is masked)
-                        default: gram_windows<kGramUnroll, (kGramUnroll <= 8 ? 1 : 2)>(gs, w0, c0, cend, lane); break;
-                    }
-                } else {
-                    gram_windows<kGramUnroll, 2>(gs, w0, c0, cend, lane);  // masked last group
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
+        gram_stream_batch<kV>(gs, cnt, t0, av, lane);
     }
     if (kWaves > 1) __syncthreads();
     else __builtin_amdgcn_wave_barrier();
 
-    // write the tile once (non-temporal: K is write-once); add_k: K already holds the dense
-    // hub-column part of these entries, and the fixed-point sum is rounded once and added to it
-    float *krow = K + r * ldk + j0;
-    const bool addk = tl.add_k;
-    const int64_t c_lo = (int64_t)dsub * (W / kSub);  // (a multiple of 8: W % 64 == 0)
-    if ((ldk & 3) == 0 && (j0 & 3) == 0) {
-        const int64_t n4 = wlen / 4;
-        f32x4 *k4 = reinterpret_cast<f32x4 *>(krow);
-        for (int64_t i = c_lo / 4 + tid; i < n4; i += 64 * kWaves) {
-            const u64x2 a = acc2[2 * i], b = acc2[2 * i + 1];
-            f32x4 o;
-            o[0] = fx_to_float(a[0], sh);
-            o[1] = fx_to_float(a[1], sh);
-            o[2] = fx_to_float(b[0], sh);
-            o[3] = fx_to_float(b[1], sh);
-            if (addk) o += __builtin_nontemporal_load(&k4[i]);
-            GRF_K_STORE(o, &k4[i]);
-        }
-        for (int64_t i = n4 * 4 + tid; i < wlen; i += 64 * kWaves)
-            krow[i] = addk ? fx_to_float(acc[i], sh) + krow[i] : fx_to_float(acc[i], sh);
-    } else {
-        // (from the row's sub-band on, as the vector path: the columns before it hold partial sums)
-        for (int64_t i = c_lo + tid; i < wlen; i += 64 * kWaves)
-            krow[i] = addk ? fx_to_float(acc[i], sh) + krow[i] : fx_to_float(acc[i], sh);
-    }
+    // write the tile once, from the row's sub-band on
+    gram_tile_out<false>(acc, K + r * ldk + j0, (ldk & 3) == 0 && (j0 & 3) == 0, (int64_t)dsub * (W / kSub), wlen, sh,
+                         tl.add_k, tid, 64 * kWaves);
 }
 
 // ------------------------------------------------- pipelined column-block tiles (GRF_REC_SLOT buckets)
@@ -513,20 +538,15 @@ __global__ __launch_bounds__(64 * kWv) void gram_slot_pipe_kernel(
     int64_t n_cols, int64_t row_begin, int64_t rows, int64_t W, int64_t t_rows, int64_t n_tiles,
     const int64_t *__restrict__ ptr, const int32_t *__restrict__ idx, const float *__restrict__ val,
     const unsigned char *__restrict__ t_rec, const int32_t *__restrict__ rowshift, float *__restrict__ K,
-    int64_t ldk, int64_t ovf_base, int32_t ablate, int64_t pad_cap, const int32_t *__restrict__ pad_cnt) {
+    int64_t ldk, int64_t ovf_base, int64_t pad_cap, const int32_t *__restrict__ pad_cnt) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];  // [W], then the waves' stream state
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-    constexpr int kV = 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t G = gridDim.x;
     const int64_t n_mine = (int64_t)blockIdx.x < n_tiles ? (n_tiles - 1 - (int64_t)blockIdx.x) / G + 1 : 0;
     u64x2 *acc2 = reinterpret_cast<u64x2 *>(acc);
     const u64x2 z2 = {0ull, 0ull};
     for (int64_t q = tid; q < W / 2; q += 64 * kWv) acc2[q] = z2;
-    unsigned char *st = reinterpret_cast<unsigned char *>(acc + W) + wave * wave_state_bytes(kV);
-    unsigned char *bidv = st;                                             // [kChunk]
-    int32_t *tbase = reinterpret_cast<int32_t *>(st + kChunk);            // [64 kV]
-    float *aval = reinterpret_cast<float *>(st + kChunk + 64 * kV * 4);  // [64 kV]
+    const GramWaveState wst = gram_wave_state(acc, W, wave, 2);  // (two virtual buckets per nonzero)
     const __amdgpu_buffer_rsrc_t rec_rs =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(t_rec), (short)0, 0x7fffffff, 0x00020000);
     auto tile_row = [&](int64_t i, int64_t &J) -> int64_t {
@@ -595,58 +615,12 @@ __global__ __launch_bounds__(64 * kWv) void gram_slot_pipe_kernel(
         tile_row(i, J);
         return *reinterpret_cast<const uint2 *>(t_rec + 32 * (J * n_cols + k));
     };
+    // one batch of 64 nonzeros (one per lane: column k, -1: none, with d = {0, 0}) whose slot headers d are loaded
     auto run_batch = [&](const GramStream &gs, int64_t J, int32_t k, float a, uint2 d) {
-        int32_t cnt[kV], excl[kV], t0[kV];
-        const int32_t sb = (int32_t)(32 * (J * n_cols + (k >= 0 ? k : 0)));
-        const int32_t inl = k >= 0 ? min((int32_t)d.x, 2) : 0;
-        t0[0] = sb + 8;
-        cnt[0] = inl;
-        t0[1] = (int32_t)ovf_base + kPairBytesG * (int32_t)d.y;
-        cnt[1] = k >= 0 ? (int32_t)d.x - inl : 0;
-        int32_t total = 0;
-#pragma unroll
-        for (int h = 0; h < kV; ++h) {
-            const int32_t inc = wave_inclusive_scan<int32_t>(cnt[h]) + total;
-            excl[h] = inc - cnt[h];
-            total = __builtin_amdgcn_readlane(inc, 63);
-        }
-#pragma unroll
-        for (int h = 0; h < kV; ++h) {
-            tbase[h * 64 + lane] = t0[h] - 12 * excl[h];
-            aval[h * 64 + lane] = a;
-        }
-        int carry = 0;
-        const int32_t chunk = total <= 256 ? 256 : total <= 512 ? 512 : kChunk;
-        for (int32_t c0 = 0; c0 < total; c0 += chunk) {
-            const int32_t cend = (total - c0) < chunk ? total : c0 + chunk;
-            if (chunk == 256) reinterpret_cast<uint32_t *>(bidv)[lane] = 0u;
-            else if (chunk == 512) reinterpret_cast<uint2 *>(bidv)[lane] = make_uint2(0u, 0u);
-            else reinterpret_cast<uint4 *>(bidv)[lane] = make_uint4(0u, 0u, 0u, 0u);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int h = 0; h < kV; ++h)
-                if (cnt[h] > 0 && excl[h] >= c0 && excl[h] < cend) bidv[excl[h] - c0] = (unsigned char)(h * 64 + lane + 1);
-            __builtin_amdgcn_wave_barrier();
-            carry = chunk == 256   ? gram_propagate_ids_n<1>(bidv, carry, lane)
-                    : chunk == 512 ? gram_propagate_ids_n<2>(bidv, carry, lane)
-                                   : gram_propagate_ids(bidv, carry, lane);
-            __builtin_amdgcn_wave_barrier();
-            int32_t w0 = c0;
-            for (; w0 + 64 * 8 <= cend; w0 += 64 * 8) gram_windows<8, 0>(gs, w0, c0, cend, lane);
-            if (w0 < cend) {
-                switch ((cend - w0 + 63) >> 6) {
-                    case 1: gram_windows<1, 1>(gs, w0, c0, cend, lane); break;
-                    case 2: gram_windows<2, 1>(gs, w0, c0, cend, lane); break;
-                    case 3: gram_windows<3, 1>(gs, w0, c0, cend, lane); break;
-                    case 4: gram_windows<4, 1>(gs, w0, c0, cend, lane); break;
-                    case 5: gram_windows<5, 1>(gs, w0, c0, cend, lane); break;
-                    case 6: gram_windows<6, 1>(gs, w0, c0, cend, lane); break;
-                    case 7: gram_windows<7, 1>(gs, w0, c0, cend, lane); break;
-                    default: gram_windows<8, 1>(gs, w0, c0, cend, lane); break;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
+        int32_t cnt[2], t0[2];
+        const float av[2] = {a, a};
+        slot_buckets(d, (int32_t)(32 * (J * n_cols + (k >= 0 ? k : 0))), (int32_t)ovf_base, t0, cnt);
+        gram_stream_batch<2>(gs, cnt, t0, av, lane);
     };
     int64_t pv = 0;
     int32_t pc = 0, shv;
@@ -666,8 +640,8 @@ __global__ __launch_bounds__(64 * kWv) void gram_slot_pipe_kernel(
         load_bounds(i + 3, pv, pc, shv);
         int64_t J;
         const int64_t row = tile_row(i, J);
-        if (ablate != 1) {
-            const GramStream gs{bidv, tbase, aval, rec_rs, reinterpret_cast<unsigned char *>(acc), ldexp(1.0, T0.sh), 8};
+        if (GRF_GRAM_PIPE_ABLATE != 1) {
+            const GramStream gs{wst, rec_rs, reinterpret_cast<unsigned char *>(acc), ldexp(1.0, T0.sh), 8};
             run_batch(gs, J, T0.k, T0.a, d0);
             for (int32_t g = 64; g < T0.nb; g += 64) {  // (a share past 64 nonzeros: batch by batch)
                 const int64_t e = T0.ws0 + g + lane;
@@ -688,29 +662,8 @@ __global__ __launch_bounds__(64 * kWv) void gram_slot_pipe_kernel(
         // tile i out (non-temporal) and its accumulator zeroed
         const int64_t r = row - row_begin, j0 = J * W;
         const int64_t wlen = (t_rows - j0) < W ? (t_rows - j0) : W;
-        const int sh = T0.sh;
-        float *krow = K + r * ldk + j0;
-        int64_t done = 0;
-        if ((ldk & 3) == 0 && (j0 & 3) == 0) {
-            const int64_t n4 = wlen / 4;
-            f32x4 *k4 = reinterpret_cast<f32x4 *>(krow);
-            for (int64_t q = tid; q < n4; q += 64 * kWv) {
-                const u64x2 x = acc2[2 * q], y = acc2[2 * q + 1];
-                f32x4 o;
-                o[0] = fx_to_float(x[0], sh);
-                o[1] = fx_to_float(x[1], sh);
-                o[2] = fx_to_float(y[0], sh);
-                o[3] = fx_to_float(y[1], sh);
-                if (ablate != 2) GRF_K_STORE(o, &k4[q]);
-                acc2[2 * q] = z2;
-                acc2[2 * q + 1] = z2;
-            }
-            done = n4 * 4;
-        }
-        for (int64_t q = done + tid; q < wlen; q += 64 * kWv) {
-            if (ablate != 2) krow[q] = fx_to_float(acc[q], sh);
-            acc[q] = 0ull;
-        }
+        gram_tile_out<true>(acc, K + r * ldk + j0, (ldk & 3) == 0 && (j0 & 3) == 0, 0, wlen, T0.sh, false, tid,
+                            64 * kWv);
         pipe_barrier();
         T0 = T1;
         d0 = d1;
@@ -845,23 +798,16 @@ __device__ __forceinline__ void gram_mirror_block_swz_at(int64_t n, int64_t bi, 
     }
 }
 
-__device__ __forceinline__ void gram_mirror_block_swz(int64_t n, int64_t nt, int64_t b, float *__restrict__ K,
-                                                      int64_t ldk, float *__restrict__ tile) {
-    int64_t bi, bj;
-    gram_mirror_tri_coords(nt, b, bi, bj);
-    gram_mirror_block_swz_at(n, bi, bj, K, ldk, tile);
-}
-
 __global__ __launch_bounds__(256) void gram_mirror_swz_kernel(int64_t n, int64_t nt, int64_t nblocks,
                                                               float *__restrict__ K, int64_t ldk) {
     __shared__ __attribute__((aligned(16))) float tile[64 * 65];
     for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
-        gram_mirror_block_swz(n, nt, b, K, ldk, tile);
+        int64_t bi, bj;
+        gram_mirror_tri_coords(nt, b, bi, bj);
+        gram_mirror_block_swz_at(n, bi, bj, K, ldk, tile);
         __syncthreads();
     }
 }
-
-__global__ void absmax_reset_kernel(float *m) { *m = 0.f; }
 
 __global__ __launch_bounds__(256) void densify_kernel(int64_t n_rows, const int64_t *__restrict__ ptr,
                                                       const int32_t *__restrict__ idx, const float *__restrict__ val,
@@ -902,180 +848,165 @@ extern "C" {
 
 size_t grf_gram_workspace_bytes(void) { return 256; }
 
-// tiles [t_first, t_last) of one Gram call
-// Equal contiguous shares of a row's nonzeros per wave (1) or round-robin batches (0): measured
-// (profiles/r03_gram_balance_ab.txt) C5's slot tiles 19.2 -> 18.4 ms per step, Enron 9.4 -> 8.7 ms,
-// C4's whole-K tiles -0.5 %; the N > 1 column blocks of line buckets (8-wave tiles, ~435 nonzeros:
-// round-robin keeps 7 waves of 64) +2..5 %, so those keep round-robin batches.
-// GRF_GRAM_BALANCE=0 / 1 forces either (A/B knob).
-static int32_t gram_balance(const GramTiles &tl, int32_t unit) {
-    static const int32_t force = [] {
-        const char *e = getenv("GRF_GRAM_BALANCE");
-        return e ? (int32_t)(atoi(e) != 0) : (int32_t)-1;
-    }();
-    if (force >= 0) return force;
-    return (unit == GRF_REC_SLOT || tl.t_rows < 0) ? 1 : 0;
+// What a Gram launch reads and writes, as the entry points fill it (see gram_sparse_kernel).
+struct GramArgs {
+    int64_t n_total;    // Phi's columns = the transpose's buckets per band
+    int64_t row_begin;  // the Phi row of the launch's local row 0 (K points at that row)
+    const int64_t *ptr; // Phi: CSR, or with pad_cap > 0 padded rows (row r's pad_cnt[r] entries at r pad_cap)
+    const int32_t *idx;
+    const float *val;
+    int64_t pad_cap;
+    const int32_t *pad_cnt;
+    int32_t unit;       // the banded transpose: GRF_REC_LINE / _PACKED / _SLOT
+    const uint32_t *t_desc;
+    const void *t_rec;
+    const void *t_split;      // sub-band split (or nullptr): read by symmetric launches only
+    const int32_t *rowshift;  // the fixed-point shift of every Phi row
+    const int32_t *row_cuts;  // 8 shares of about equal record pairs per row (or nullptr)
+    float *K;
+    int64_t ldk;
+    hipStream_t st;
+};
+
+// One argument check for the row, sym, upper, kslice and cols entries (fn: the entry's name; args_ok: its own
+// pointer and range conditions; ld_min: the columns a K row holds).
+static int32_t gram_check(const char *fn, bool args_ok, int32_t unit, const void *t_rec, int64_t ldk, int64_t ld_min,
+                          int64_t band_width) {
+    GRF_REQUIRE(args_ok, GRF_EINVAL, "%s: bad arguments", fn);
+    GRF_REQUIRE(unit == GRF_REC_LINE || unit == GRF_REC_PACKED || unit == GRF_REC_SLOT, GRF_EINVAL,
+                "%s: rec_unit must be GRF_REC_LINE, GRF_REC_PACKED or GRF_REC_SLOT", fn);
+    GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL, "%s: t_rec must be 128-byte aligned", fn);
+    GRF_REQUIRE(ldk >= ld_min, GRF_EINVAL, "%s: ldk < %lld columns", fn, (long long)ld_min);
+    GRF_REQUIRE(band_width >= 64 && band_width % 64 == 0 && band_width <= 8192, GRF_EUNSUPPORTED,
+                "%s: band_width must be a multiple of 64 in [64, 8192]", fn);
+    return GRF_OK;
 }
 
-static int32_t gram_tiles_launch(int64_t n_total, int64_t row_begin, const GramTiles &tl, int64_t t_first,
-                                 int64_t t_last, const int64_t *ptr, const int32_t *idx, const float *val,
-                                 const uint32_t *t_desc, const void *t_rec, int32_t unit, const int32_t *t_rowshift,
-                                 float *K, int64_t ldk, hipStream_t st, const void *t_split = nullptr,
-                                 int64_t slot_buckets = 0, const int32_t *row_cuts = nullptr, int64_t pad_cap = 0,
-                                 const int32_t *pad_cnt = nullptr) {
-    if (unit == GRF_REC_SLOT) {
-        // the slot layout: 8-wave tiles (one batch of 64 nonzeros per wave: two stream buckets each),
-        // the default unroll and exact tails; the overflow pairs follow the slot_buckets slots
-        GRF_REQUIRE(!t_split, GRF_EUNSUPPORTED, "gram: GRF_REC_SLOT has no split variant");
-        GRF_REQUIRE(32 * slot_buckets < ((int64_t)1 << 30), GRF_EUNSUPPORTED,
+// tiles [t_first, t_last) of one Gram call
+static int32_t gram_tiles_launch(const GramArgs &a, const GramTiles &tl, int64_t t_first, int64_t t_last) {
+    const bool slot = a.unit == GRF_REC_SLOT;
+    const unsigned char *rec = reinterpret_cast<const unsigned char *>(a.t_rec);
+    const int64_t ovf_base = slot ? 32 * tl.nb * a.n_total : 0;  // the overflow pairs follow the slots of all buckets
+    if (slot) {
+        GRF_REQUIRE(!a.t_split, GRF_EUNSUPPORTED, "gram: GRF_REC_SLOT has no split variant");
+        GRF_REQUIRE(ovf_base < ((int64_t)1 << 30), GRF_EUNSUPPORTED,
                     "gram: GRF_REC_SLOT slots beyond 32-bit record offsets");
         // column blocks (a whole launch of non-symmetric tiles over all columns): the persistent software-pipelined
-        // kernel, GRF_GRAM_PIPE=0: the tile-per-workgroup kernel below (read per call: the bit-identity test
-        // switches it; GRF_GRAM_PIPE_ABLATE=1 / 2 are timing-only ablations -- no gathers / no K stores -- whose
-        // K is wrong; profiles/r06_c5_gram_ab.txt)
+        // kernel, GRF_GRAM_PIPE=0: the tile-per-workgroup kernel below (read per call: the bit-identity tests
+        // switch it)
         const bool pipe = [] {
             const char *e = getenv("GRF_GRAM_PIPE");
             return !e || atoi(e) != 0;
         }();
-        const int32_t ablate = [] {
-            const char *e = getenv("GRF_GRAM_PIPE_ABLATE");
-            return e ? (int32_t)atoi(e) : 0;
-        }();
         const bool pipe_ok = !tl.sym && tl.t_rows >= 0 && !tl.add_k && tl.k_begin == 0 &&
-                             tl.k_end == (int32_t)n_total && t_first == 0 && t_last == tl.total() && tl.J_off == 0;
-        GRF_REQUIRE(pad_cap == 0 || pipe_ok, GRF_EUNSUPPORTED,
+                             tl.k_end == (int32_t)a.n_total && t_first == 0 && t_last == tl.total() && tl.J_off == 0;
+        GRF_REQUIRE(a.pad_cap == 0 || pipe_ok, GRF_EUNSUPPORTED,
                     "gram: padded rows need the pipelined column-block kernel (a whole non-symmetric launch)");
-        if ((pipe || pad_cap > 0) && pipe_ok) {
+        if ((pipe || a.pad_cap > 0) && pipe_ok) {
             const size_t lds = gram_lds_bytes(tl.W, 8, 2);
             int dev = 0, n_cu = 0;
             GRF_CHECK_HIP(hipGetDevice(&dev));
             GRF_CHECK_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
             const int per_cu = (int)std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)lds);
             const int64_t grid = std::min<int64_t>((int64_t)std::max(n_cu, 1) * per_cu, t_last);
-            gram_slot_pipe_kernel<8><<<(unsigned)grid, 512, lds, st>>>(
-                n_total, row_begin, tl.rows, tl.W, tl.t_rows, t_last, ptr, idx, val,
-                reinterpret_cast<const unsigned char *>(t_rec), t_rowshift, K, ldk, 32 * slot_buckets, ablate, pad_cap,
-                pad_cnt);
+            gram_slot_pipe_kernel<8><<<(unsigned)grid, 512, lds, a.st>>>(
+                a.n_total, a.row_begin, tl.rows, tl.W, tl.t_rows, t_last, a.ptr, a.idx, a.val, rec, a.rowshift, a.K,
+                a.ldk, ovf_base, a.pad_cap, a.pad_cnt);
             GRF_CHECK_LAUNCH("gram_slot_pipe_kernel");
             return GRF_OK;
         }
-        const size_t lds = gram_lds_bytes(tl.W, 8, 2);
-        const int64_t max_tiles = ((1ll << 32) - 1) / (64 * 8);
-        for (int64_t t0 = t_first; t0 < t_last; t0 += max_tiles) {
-            const int64_t nt = (t_last - t0) < max_tiles ? (t_last - t0) : max_tiles;
-            gram_sparse_kernel<8, 1, 8, true, true><<<(unsigned)nt, 512, lds, st>>>(
-                n_total, row_begin, tl, t0, ptr, idx, val, reinterpret_cast<const uint2 *>(t_desc),
-                reinterpret_cast<const unsigned char *>(t_rec), unit, t_rowshift, K, ldk, nullptr,
-                32 * slot_buckets, gram_balance(tl, unit), nullptr);
-            GRF_CHECK_LAUNCH("gram_sparse_kernel");
-        }
-        return GRF_OK;
     }
-    // GRF_GRAM_SPLIT=0: ignore the sub-band split (A/B of the diagonal tiles' skip)
-    static const bool use_split = [] {
-        const char *e = getenv("GRF_GRAM_SPLIT");
-        return !e || atoi(e) != 0;
-    }();
-    const uint16_t *split = (use_split && tl.sym) ? (const uint16_t *)t_split : nullptr;
+    // the sub-band split: diagonal tiles of symmetric launches skip the pairs before the row's sub-band
+    const uint16_t *split = tl.sym ? (const uint16_t *)a.t_split : nullptr;
     // waves per tile: 4 for W <= 4096 (4 tiles of 40 KiB per CU), 8 for wider bands (2 tiles of
-    // 76 KiB per CU: 16 waves per CU either way); measured best at both widths (GRF_GRAM_WAVES=4/8
-    // overrides); 8 windows of gathers in flight per wave and an exact-size last window group (the
-    // round-1..3 sweeps of 4 / 16 windows and of masked tails: profiles/AB_LOG.md)
-    static const int env_waves = [] {
-        const char *w = getenv("GRF_GRAM_WAVES");
-        const int ww = w ? atoi(w) : 0;
-        return ww == 8 ? 8 : ww == 4 ? 4 : 0;
-    }();
-    const int waves = env_waves ? env_waves : (tl.W > 4096 ? 8 : 4);
-    const size_t lds = gram_lds_bytes(tl.W, waves, waves == 8 ? 1 : 2);
+    // 76 KiB per CU: 16 waves per CU either way); measured best at both widths; slot buckets: 8 waves
+    // (one batch of 64 nonzeros per wave: two stream buckets each).  8 windows of gathers in flight per wave
+    // and an exact-size last window group (the round-1..3 sweeps of 4 / 16 windows and of masked tails:
+    // profiles/AB_LOG.md)
+    const int waves = (slot || tl.W > 4096) ? 8 : 4;
+    const size_t lds = gram_lds_bytes(tl.W, waves, (slot || waves == 4) ? 2 : 1);
+    // Equal contiguous shares of a row's nonzeros per wave (1) or round-robin batches (0): measured
+    // (profiles/r03_gram_balance_ab.txt) C5's slot tiles 19.2 -> 18.4 ms per step, Enron 9.4 -> 8.7 ms,
+    // C4's whole-K tiles -0.5 %; the N > 1 column blocks of line buckets (8-wave tiles, ~435 nonzeros:
+    // round-robin keeps 7 waves of 64) +2..5 %, so those keep round-robin batches.
+    const int32_t balance = (slot || tl.t_rows < 0) ? 1 : 0;
     // one launch covers at most 2^32 - 1 work-items: split the tile range
     const int64_t max_tiles = ((1ll << 32) - 1) / (64 * waves);
     for (int64_t t0 = t_first; t0 < t_last; t0 += max_tiles) {
         const int64_t nt = (t_last - t0) < max_tiles ? (t_last - t0) : max_tiles;
-#define GRF_GRAM_LAUNCH(WV, H)                                                                                    \
-    gram_sparse_kernel<WV, H, 8, true><<<(unsigned)nt, 64 * WV, lds, st>>>(                                       \
-        n_total, row_begin, tl, t0, ptr, idx, val, reinterpret_cast<const uint2 *>(t_desc),                       \
-        reinterpret_cast<const unsigned char *>(t_rec), unit, t_rowshift, K, ldk, split, 0, gram_balance(tl, unit), \
-        row_cuts)
-        if (waves == 8) GRF_GRAM_LAUNCH(8, 1);
-        else GRF_GRAM_LAUNCH(4, 2);
+#define GRF_GRAM_LAUNCH(WV, H, SLOT)                                                                              \
+    gram_sparse_kernel<WV, H, SLOT><<<(unsigned)nt, 64 * WV, lds, a.st>>>(                                        \
+        a.n_total, a.row_begin, tl, t0, a.ptr, a.idx, a.val, reinterpret_cast<const uint2 *>(a.t_desc), rec, a.unit, \
+        a.rowshift, a.K, a.ldk, split, ovf_base, balance, a.row_cuts)
+        if (slot) GRF_GRAM_LAUNCH(8, 1, true);
+        else if (waves == 8) GRF_GRAM_LAUNCH(8, 1, false);
+        else GRF_GRAM_LAUNCH(4, 2, false);
 #undef GRF_GRAM_LAUNCH
         GRF_CHECK_LAUNCH("gram_sparse_kernel");
     }
     return GRF_OK;
 }
 
-static int32_t gram_sparse_launch(int64_t n_total, int64_t row_begin, int64_t rows, bool sym, int64_t k_begin,
-                                  int64_t k_end, const int64_t *ptr, const int32_t *idx, const float *val,
-                                  int64_t band_width, int32_t unit, const uint32_t *t_desc, const void *t_rec,
-                                  const int32_t *t_rowshift, float *K, int64_t ldk, hipStream_t st,
-                                  const void *t_split = nullptr) {
-    const int64_t nb = cdiv<int64_t>(n_total, band_width);
-    const GramTiles tl{rows, band_width, nb, sym, (int32_t)k_begin, (int32_t)k_end};
-    const int64_t n_tiles = tl.total();
-    if (n_tiles == 0) return GRF_OK;
-    return gram_tiles_launch(n_total, row_begin, tl, 0, n_tiles, ptr, idx, val, t_desc, t_rec, unit, t_rowshift, K,
-                             ldk, st, t_split, nb * n_total);
-}
-
-static int32_t gram_sparse_check(int64_t n_total, int64_t row_begin, int64_t row_end, const int64_t *ptr,
-                                 int64_t band_width, int32_t unit, const uint32_t *t_desc, const void *t_rec,
-                                 const int32_t *t_rowshift, float *K, int64_t ldk) {
-    GRF_REQUIRE(unit == GRF_REC_LINE || unit == GRF_REC_PACKED || unit == GRF_REC_SLOT, GRF_EINVAL,
-                "grf_gram_sparse: rec_unit must be GRF_REC_LINE, GRF_REC_PACKED or GRF_REC_SLOT");
-    GRF_REQUIRE(n_total >= 0 && 0 <= row_begin && row_begin <= row_end && row_end <= n_total && ptr && t_desc && K &&
-                    t_rowshift && t_rec,
-                GRF_EINVAL, "grf_gram_sparse: bad arguments");
-    GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL, "grf_gram_sparse: t_rec must be 128-byte aligned");
-    GRF_REQUIRE(ldk >= n_total, GRF_EINVAL, "grf_gram_sparse: ldk < n");
-    GRF_REQUIRE(band_width >= 64 && band_width % 64 == 0 && band_width <= 8192, GRF_EUNSUPPORTED,
-                "grf_gram_sparse: band_width must be a multiple of 64 in [64, 8192]");
-    return GRF_OK;
+// the rows [row_begin, row_end) of K = Phi Phi^T against Phi's own transpose, from the columns [k_begin, k_end)
+static int32_t gram_sparse_rows_impl(const char *fn, int64_t n_total, int64_t row_begin, int64_t row_end,
+                                     int64_t k_begin, int64_t k_end, const int64_t *ptr, const int32_t *idx,
+                                     const float *val, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
+                                     const void *t_rec, const int32_t *t_rowshift, float *K, int64_t ldk,
+                                     grf_stream_t stream) {
+    int32_t rc = gram_check(fn,
+                            n_total >= 0 && 0 <= row_begin && row_begin <= row_end && row_end <= n_total && ptr &&
+                                t_desc && K && t_rowshift && t_rec,
+                            rec_unit, t_rec, ldk, n_total, band_width);
+    if (rc != GRF_OK) return rc;
+    GRF_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= n_total, GRF_EINVAL, "%s: bad column slice [%lld, %lld)",
+                fn, (long long)k_begin, (long long)k_end);
+    if (row_end == row_begin || n_total == 0) return GRF_OK;
+    const GramTiles tl{row_end - row_begin, band_width, cdiv<int64_t>(n_total, band_width), false, (int32_t)k_begin,
+                       (int32_t)k_end};
+    const GramArgs a{n_total,  row_begin, ptr,   idx,     val,        0,       nullptr,  //
+                     rec_unit, t_desc,    t_rec, nullptr, t_rowshift, nullptr, K, ldk, S(stream)};
+    return gram_tiles_launch(a, tl, 0, tl.total());
 }
 
 int32_t grf_gram_sparse(int64_t n_total, int64_t row_begin, int64_t row_end, const int64_t *ptr, const int32_t *idx,
                         const float *val, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
                         const void *t_rec, const int32_t *t_rowshift, float *K, int64_t ldk, void *workspace,
                         size_t workspace_bytes, grf_stream_t stream) {
-    int32_t rc = gram_sparse_check(n_total, row_begin, row_end, ptr, band_width, rec_unit, t_desc, t_rec, t_rowshift,
-                                   K, ldk);
-    if (rc != GRF_OK) return rc;
-    if (row_end == row_begin || n_total == 0) return GRF_OK;
-    return gram_sparse_launch(n_total, row_begin, row_end - row_begin, false, 0, n_total, ptr, idx, val, band_width,
-                              rec_unit, t_desc, t_rec, t_rowshift, K, ldk, S(stream));
+    return gram_sparse_rows_impl("grf_gram_sparse", n_total, row_begin, row_end, 0, n_total, ptr, idx, val, band_width,
+                                 rec_unit, t_desc, t_rec, t_rowshift, K, ldk, stream);
 }
 
-int32_t grf_gram_sparse_sym(int64_t n_total, const int64_t *ptr, const int32_t *idx, const float *val,
-                            int64_t band_width, int32_t rec_unit, const uint32_t *t_desc, const void *t_rec,
-                            const void *t_split, const int32_t *t_rowshift, float *K, int64_t ldk, void *workspace, size_t workspace_bytes,
-                            grf_stream_t stream) {
-    int32_t rc = gram_sparse_check(n_total, 0, n_total, ptr, band_width, rec_unit, t_desc, t_rec, t_rowshift, K, ldk);
-    if (rc != GRF_OK) return rc;
-    if (n_total == 0) return GRF_OK;
-    rc = gram_sparse_launch(n_total, 0, n_total, true, 0, n_total, ptr, idx, val, band_width, rec_unit, t_desc, t_rec,
-                            t_rowshift, K, ldk, S(stream), t_split);
-    if (rc != GRF_OK) return rc;
-    return grf_gram_mirror(n_total, K, ldk, 0, stream);
-}
-
-static int32_t gram_sparse_upper_impl(int64_t n_total, const int64_t *ptr, const int32_t *idx, const float *val,
-                                      int64_t band_width, int32_t rec_unit, const uint32_t *t_desc, const void *t_rec,
-                                      const void *t_split, const int32_t *t_rowshift, float *K, int64_t ldk, int32_t part_begin,
-                                      int32_t part_end, int32_t n_parts, bool add_k, grf_stream_t stream,
-                                      const int32_t *row_cuts = nullptr) {
-    int32_t rc = gram_sparse_check(n_total, 0, n_total, ptr, band_width, rec_unit, t_desc, t_rec, t_rowshift, K, ldk);
+// the whole K's tiles on and above the diagonal band, in parts [part_begin, part_end) of n_parts
+static int32_t gram_sparse_upper_impl(const char *fn, int64_t n_total, const int64_t *ptr, const int32_t *idx,
+                                      const float *val, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
+                                      const void *t_rec, const void *t_split, const int32_t *t_rowshift,
+                                      const int32_t *row_cuts, float *K, int64_t ldk, int32_t part_begin,
+                                      int32_t part_end, int32_t n_parts, bool add_k, grf_stream_t stream) {
+    int32_t rc = gram_check(fn, n_total >= 0 && ptr && t_desc && K && t_rowshift && t_rec, rec_unit, t_rec, ldk,
+                            n_total, band_width);
     if (rc != GRF_OK) return rc;
     GRF_REQUIRE(n_parts >= 1 && 0 <= part_begin && part_begin <= part_end && part_end <= n_parts, GRF_EINVAL,
-                "grf_gram_sparse_upper: bad tile parts [%d, %d) of %d", part_begin, part_end, n_parts);
+                "%s: bad tile parts [%d, %d) of %d", fn, part_begin, part_end, n_parts);
     if (n_total == 0 || part_begin == part_end) return GRF_OK;
     GramTiles tl{n_total, band_width, cdiv<int64_t>(n_total, band_width), true, 0, (int32_t)n_total};
     tl.add_k = add_k;
     const int64_t total = tl.total();
     const int64_t t0 = total * part_begin / n_parts, t1 = total * part_end / n_parts;
     if (t1 <= t0) return GRF_OK;
-    GRF_REQUIRE(!row_cuts || rec_unit != GRF_REC_SLOT, GRF_EUNSUPPORTED, "grf_gram_sparse_upper: row cuts with slot buckets");
-    return gram_tiles_launch(n_total, 0, tl, t0, t1, ptr, idx, val, t_desc, t_rec, rec_unit, t_rowshift, K, ldk,
-                             S(stream), t_split, tl.nb * n_total, row_cuts);
+    GRF_REQUIRE(!row_cuts || rec_unit != GRF_REC_SLOT, GRF_EUNSUPPORTED, "%s: row cuts with slot buckets", fn);
+    const GramArgs a{n_total,  0,      ptr,   idx,     val,        0,        nullptr,  //
+                     rec_unit, t_desc, t_rec, t_split, t_rowshift, row_cuts, K, ldk, S(stream)};
+    return gram_tiles_launch(a, tl, t0, t1);
+}
+
+int32_t grf_gram_sparse_sym(int64_t n_total, const int64_t *ptr, const int32_t *idx, const float *val,
+                            int64_t band_width, int32_t rec_unit, const uint32_t *t_desc, const void *t_rec,
+                            const void *t_split, const int32_t *t_rowshift, float *K, int64_t ldk, void *workspace, size_t workspace_bytes,
+                            grf_stream_t stream) {
+    int32_t rc = gram_sparse_upper_impl("grf_gram_sparse_sym", n_total, ptr, idx, val, band_width, rec_unit, t_desc,
+                                        t_rec, t_split, t_rowshift, nullptr, K, ldk, 0, 1, 1, false, stream);
+    if (rc != GRF_OK || n_total == 0) return rc;
+    return grf_gram_mirror(n_total, K, ldk, 0, stream);
 }
 
 int32_t grf_gram_sparse_upper_ex(int64_t n_total, const int64_t *ptr, const int32_t *idx, const float *val,
@@ -1083,8 +1014,9 @@ int32_t grf_gram_sparse_upper_ex(int64_t n_total, const int64_t *ptr, const int3
                                  const void *t_split, const int32_t *t_rowshift, const int32_t *row_cuts, float *K,
                                  int64_t ldk, int32_t part_begin, int32_t part_end, int32_t n_parts, int32_t add_k,
                                  grf_stream_t stream) {
-    return gram_sparse_upper_impl(n_total, ptr, idx, val, band_width, rec_unit, t_desc, t_rec, t_split, t_rowshift,
-                                  K, ldk, part_begin, part_end, n_parts, add_k != 0, stream, row_cuts);
+    return gram_sparse_upper_impl("grf_gram_sparse_upper_ex", n_total, ptr, idx, val, band_width, rec_unit, t_desc,
+                                  t_rec, t_split, t_rowshift, row_cuts, K, ldk, part_begin, part_end, n_parts,
+                                  add_k != 0, stream);
 }
 
 // ---------------------------------------------------------------- wave shares by record pairs
@@ -1157,8 +1089,8 @@ int32_t grf_gram_sparse_upper(int64_t n_total, const int64_t *ptr, const int32_t
                               const void *t_split, const int32_t *t_rowshift, float *K, int64_t ldk, int32_t part_begin,
                               int32_t part_end, int32_t n_parts, void *workspace, size_t workspace_bytes,
                               grf_stream_t stream) {
-    return gram_sparse_upper_impl(n_total, ptr, idx, val, band_width, rec_unit, t_desc, t_rec, t_split, t_rowshift,
-                                  K, ldk, part_begin, part_end, n_parts, false, stream);
+    return gram_sparse_upper_impl("grf_gram_sparse_upper", n_total, ptr, idx, val, band_width, rec_unit, t_desc, t_rec,
+                                  t_split, t_rowshift, nullptr, K, ldk, part_begin, part_end, n_parts, false, stream);
 }
 
 int32_t grf_gram_sparse_upper_add(int64_t n_total, const int64_t *ptr, const int32_t *idx, const float *val,
@@ -1167,8 +1099,9 @@ int32_t grf_gram_sparse_upper_add(int64_t n_total, const int64_t *ptr, const int
                                   int32_t part_begin,
                                   int32_t part_end, int32_t n_parts, void *workspace, size_t workspace_bytes,
                                   grf_stream_t stream) {
-    return gram_sparse_upper_impl(n_total, ptr, idx, val, band_width, rec_unit, t_desc, t_rec, t_split, t_rowshift,
-                                  K, ldk, part_begin, part_end, n_parts, true, stream);
+    return gram_sparse_upper_impl("grf_gram_sparse_upper_add", n_total, ptr, idx, val, band_width, rec_unit, t_desc,
+                                  t_rec, t_split, t_rowshift, nullptr, K, ldk, part_begin, part_end, n_parts, true,
+                                  stream);
 }
 
 int32_t grf_hub_panel(int64_t n_rows, const int64_t *ptr, const int32_t *idx, const float *val,
@@ -1200,21 +1133,19 @@ int32_t grf_transpose_drop_columns(int64_t n_bands, int64_t n_cols, uint32_t *t_
 // against the t_rows rows of another matrix Phi_B (a rank's own rows) whose banded transpose is
 // given; the row shifts come from grf_phi_row_shifts over all of Phi.  With Phi_B = Phi[b:e] this
 // is K[:, b:e] -- entry for entry the row mode's K[r, b + j] -- so a rank transposes only its rows.
-static int32_t gram_sparse_cols_impl(int64_t n_cols, int64_t row_begin, int64_t row_end, const int64_t *ptr,
-                                     const int32_t *idx, const float *val, const int32_t *row_shift, int64_t t_rows,
+static int32_t gram_sparse_cols_impl(const char *fn, int64_t n_cols, int64_t row_begin, int64_t row_end,
+                                     const int64_t *ptr, const int32_t *idx, const float *val, int64_t pad_cap,
+                                     const int32_t *pad_cnt, const int32_t *row_shift, int64_t t_rows,
                                      int64_t sym_row0, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
                                      const void *t_rec, const void *t_split, float *K, int64_t ldk,
-                                     grf_stream_t stream, int64_t pad_cap = 0, const int32_t *pad_cnt = nullptr) {
-    GRF_REQUIRE(n_cols > 0 && 0 <= row_begin && row_begin <= row_end && (ptr || pad_cnt) && idx && val && row_shift &&
-                    t_rows >= 0 && t_desc && t_rec && K && ldk >= t_rows,
-                GRF_EINVAL, "grf_gram_sparse_cols: bad arguments");
-    GRF_REQUIRE(band_width >= 64 && band_width % 64 == 0 && band_width <= 8192, GRF_EUNSUPPORTED,
-                "grf_gram_sparse_cols: band_width must be a multiple of 64 in [64, 8192]");
-    GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL, "grf_gram_sparse_cols: t_rec must be 128-byte aligned");
-    GRF_REQUIRE(rec_unit == GRF_REC_LINE || rec_unit == GRF_REC_PACKED || rec_unit == GRF_REC_SLOT, GRF_EINVAL,
-                "grf_gram_sparse_cols: bad rec_unit");
+                                     grf_stream_t stream) {
+    int32_t rc = gram_check(fn,
+                            n_cols > 0 && 0 <= row_begin && row_begin <= row_end && (ptr || pad_cnt) && idx && val &&
+                                row_shift && t_rows >= 0 && t_desc && t_rec && K,
+                            rec_unit, t_rec, ldk, t_rows, band_width);
+    if (rc != GRF_OK) return rc;
     GRF_REQUIRE(sym_row0 < 0 || (row_begin <= sym_row0 && sym_row0 + t_rows <= row_end), GRF_EINVAL,
-                "grf_gram_sparse_cols: the symmetric square [sym_row0, sym_row0 + t_rows) must lie in the rows");
+                "%s: the symmetric square [sym_row0, sym_row0 + t_rows) must lie in the rows", fn);
     if (row_end == row_begin || t_rows == 0) return GRF_OK;
     const int64_t nb = cdiv<int64_t>(t_rows, band_width);
     hipStream_t st = S(stream);
@@ -1223,14 +1154,15 @@ static int32_t gram_sparse_cols_impl(int64_t n_cols, int64_t row_begin, int64_t 
         if (r1 <= r0) return GRF_OK;
         GramTiles tl{r1 - r0, band_width, nb, sym, 0, (int32_t)n_cols};
         tl.t_rows = t_rows;
-        return gram_tiles_launch(n_cols, r0, tl, 0, tl.total(), ptr, idx, val, t_desc, t_rec, rec_unit, row_shift,
-                                 K + (r0 - row_begin) * ldk, ldk, st, sym ? t_split : nullptr, nb * n_cols, nullptr,
-                                 pad_cap, pad_cnt);
+        const GramArgs a{n_cols,   r0,     ptr,   idx,                     val,       pad_cap, pad_cnt,  //
+                         rec_unit, t_desc, t_rec, sym ? t_split : nullptr, row_shift, nullptr,
+                         K + (r0 - row_begin) * ldk, ldk, st};
+        return gram_tiles_launch(a, tl, 0, tl.total());
     };
     if (sym_row0 < 0) return launch(row_begin, row_end, false);
     // Phi_B = Phi[sym_row0, sym_row0 + t_rows): the square K[B, B] is symmetric and its bands start at
     // sym_row0, so only its tiles on and above the diagonal run (symmetric enumeration), then a mirror
-    int32_t rc = launch(sym_row0, sym_row0 + t_rows, true);
+    rc = launch(sym_row0, sym_row0 + t_rows, true);
     if (rc == GRF_OK) rc = launch(row_begin, sym_row0, false);
     if (rc == GRF_OK) rc = launch(sym_row0 + t_rows, row_end, false);
     if (rc != GRF_OK) return rc;
@@ -1244,8 +1176,9 @@ int32_t grf_gram_sparse_cols(int64_t n_cols, int64_t row_begin, int64_t row_end,
                              size_t workspace_bytes, grf_stream_t stream) {
     (void)workspace;
     (void)workspace_bytes;
-    return gram_sparse_cols_impl(n_cols, row_begin, row_end, ptr, idx, val, row_shift, t_rows, sym_row0, band_width,
-                                 rec_unit, t_desc, t_rec, t_split, K, ldk, stream);
+    return gram_sparse_cols_impl("grf_gram_sparse_cols", n_cols, row_begin, row_end, ptr, idx, val, 0, nullptr,
+                                 row_shift, t_rows, sym_row0, band_width, rec_unit, t_desc, t_rec, t_split, K, ldk,
+                                 stream);
 }
 
 int32_t grf_gram_sparse_cols_padded(int64_t n_cols, int64_t row_begin, int64_t row_end, int64_t cap,
@@ -1253,8 +1186,9 @@ int32_t grf_gram_sparse_cols_padded(int64_t n_cols, int64_t row_begin, int64_t r
                                     int64_t t_rows, int64_t band_width, const uint32_t *t_desc, const void *t_rec,
                                     float *K, int64_t ldk, grf_stream_t stream) {
     GRF_REQUIRE(cap >= 1 && cnt, GRF_EINVAL, "grf_gram_sparse_cols_padded: bad padded rows");
-    return gram_sparse_cols_impl(n_cols, row_begin, row_end, nullptr, idx, val, row_shift, t_rows, -1, band_width,
-                                 GRF_REC_SLOT, t_desc, t_rec, nullptr, K, ldk, stream, cap, cnt);
+    return gram_sparse_cols_impl("grf_gram_sparse_cols_padded", n_cols, row_begin, row_end, nullptr, idx, val, cap,
+                                 cnt, row_shift, t_rows, -1, band_width, GRF_REC_SLOT, t_desc, t_rec, nullptr, K, ldk,
+                                 stream);
 }
 
 int32_t grf_gram_sparse_kslice(int64_t n_total, int64_t row_begin, int64_t row_end, int64_t k_begin, int64_t k_end,
@@ -1262,16 +1196,10 @@ int32_t grf_gram_sparse_kslice(int64_t n_total, int64_t row_begin, int64_t row_e
                                int32_t rec_unit, const uint32_t *t_desc, const void *t_rec,
                                const int32_t *t_rowshift, float *K, int64_t ldk, void *workspace,
                                size_t workspace_bytes, grf_stream_t stream) {
-    int32_t rc = gram_sparse_check(n_total, row_begin, row_end, ptr, band_width, rec_unit, t_desc, t_rec, t_rowshift,
-                                   K, ldk);
-    if (rc != GRF_OK) return rc;
-    GRF_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= n_total, GRF_EINVAL,
-                "grf_gram_sparse_kslice: bad column slice [%lld, %lld)", (long long)k_begin, (long long)k_end);
-    if (row_end == row_begin || n_total == 0) return GRF_OK;
     (void)workspace;
     (void)workspace_bytes;
-    return gram_sparse_launch(n_total, row_begin, row_end - row_begin, false, k_begin, k_end, ptr, idx, val,
-                              band_width, rec_unit, t_desc, t_rec, t_rowshift, K, ldk, S(stream));
+    return gram_sparse_rows_impl("grf_gram_sparse_kslice", n_total, row_begin, row_end, k_begin, k_end, ptr, idx, val,
+                                 band_width, rec_unit, t_desc, t_rec, t_rowshift, K, ldk, stream);
 }
 
 int32_t grf_gram_mirror(int64_t n, float *K, int64_t ldk, int64_t max_workgroups, grf_stream_t stream) {
@@ -1279,13 +1207,8 @@ int32_t grf_gram_mirror(int64_t n, float *K, int64_t ldk, int64_t max_workgroups
     if (n == 0) return GRF_OK;
     const int64_t nt = cdiv<int64_t>(n, 64), blocks = nt * (nt + 1) / 2;
     // workgroups: one per block (max_workgroups <= 0), or a bounded grid-stride grid that leaves CU
-    // slots to another stream (GRF_MIRROR_WGS overrides, for experiments)
-    static const int64_t env_cap = [] {
-        const char *e = getenv("GRF_MIRROR_WGS");
-        return e ? (int64_t)atoll(e) : (int64_t)-1;
-    }();
-    const int64_t cap = env_cap >= 0 ? env_cap : max_workgroups;
-    const int64_t grid = cap > 0 && cap < blocks ? cap : blocks;
+    // slots to another stream
+    const int64_t grid = max_workgroups > 0 && max_workgroups < blocks ? max_workgroups : blocks;
     GRF_REQUIRE_GRID(grid, 256, "gram_mirror_swz_kernel");
     gram_mirror_swz_kernel<<<(unsigned)grid, 256, 0, S(stream)>>>(n, nt, blocks, K, ldk);
     GRF_CHECK_LAUNCH("gram_mirror_swz_kernel");

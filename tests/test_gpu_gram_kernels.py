@@ -423,6 +423,26 @@ def test_gram_cols_slot_bitwise(eng, cols_ref, pipe, monkeypatch):
         assert {1, 2} <= owned and max(owned) >= 4, owned
 
 
+@pytest.mark.parametrize("pipe", ["0", "1"])
+def test_gram_cols_slot_long_streams_bitwise(eng, pipe, monkeypatch):
+    """probe_W8192 through the column-block entry (PB = P, rows [0, row_end), no symmetric square): its 8 waves of
+    equal contiguous shares are the pipelined kernel's share rule, so that kernel -- otherwise run on streams of a
+    few pairs -- meets the 512 and 1024 chunks, the carry across chunks and every tail window count.  Same
+    reference rows as test_gram_sparse_rows_bitwise[probe_W8192-slot]; ldk % 4 == 0 (vector write-out) and != 0."""
+    c = _case("probe_W8192")
+    sh = c.shifts[0]
+    ref = _ref_rows(c, sh, "rule")
+    rb, re, n = c.row_begin, c.row_end, c.n
+    assert rb == 0 and c.edges["waves"] == 8
+    monkeypatch.setenv("GRF_GRAM_PIPE", pipe)
+    d = Dev(eng, c.P, c.W, "slot", seed=13, PB=c.P, shifts=sh)
+    for ldk in (n + 4, n + 1):
+        got = _body(_gram_cols(eng, d, rb, re, -1, ldk), re - rb, ldk, n, "probe_W8192 cols")
+        bad = np.argwhere(_bits(got) != _bits(ref))
+        print(f"cols/slot probe_W8192 pipe={pipe} ldk={ldk}: rows [{rb}, {re}) x {n} columns, {len(bad)} differ")
+        assert len(bad) == 0, (pipe, ldk, len(bad), bad[:5].tolist(), [(got[i, j], ref[i, j]) for i, j in bad[:5]])
+
+
 def test_gram_cols_padded_bitwise(eng, cols_ref):
     """Padded rows (cnt = 0 and cnt == cap among them) give the CSR path's bits."""
     P, PB, sh, ref = cols_ref

@@ -1,7 +1,9 @@
 """C5 column-block Gram alone (bench.py --workload c5's K assembly: 1M rows x the 8192-column slot block),
-under a list of kernel knob settings read per call by the library (GRF_GRAM_PIPE, GRF_GRAM_PIPE_G,
-GRF_GRAM_PIPE_ABLATE): HIP-event ms per launch (mean of reps, alternating rounds) and the K block's
-fingerprint (tools/gram_hash.py; identical = identical bits; ablations are timing-only).
+under a list of kernel knob settings read per call by the library (GRF_GRAM_PIPE): HIP-event ms per launch
+(mean of reps, alternating rounds) and the K block's fingerprint (tools/gram_hash.py; identical = identical bits).
+The timing-only ablations of the pipelined kernel (no gathers / no K stores: a wrong K) are separate builds of the
+library, ``make EXTRA=-DGRF_GRAM_PIPE_ABLATE=1`` (or ``=2``) into a copy of the tree; run this tool once per
+library, each in its own process, with GRF_AMD_LIB pointing at it, and compare the ms (not the fingerprints).
 usage: c5_gram_ab.py [reps] [rounds] [cfg ...]   cfg = comma-separated VAR=value list ("base" = none)"""
 import json
 import os
@@ -17,7 +19,7 @@ from grf_amd.engine import DeviceCSR, GRFEngine  # noqa: E402
 from grf_amd.graphs import powerlaw_graph  # noqa: E402
 from tools.gram_hash import fingerprint  # noqa: E402
 
-KNOBS = ("GRF_GRAM_PIPE", "GRF_GRAM_PIPE_G", "GRF_GRAM_PIPE_ABLATE")
+KNOBS = ("GRF_GRAM_PIPE",)
 
 
 def main():
@@ -49,7 +51,7 @@ def main():
             ev[1].record()
             ev[1].synchronize()
             res[c].append(ev[0].elapsed_time(ev[1]) / reps)
-            if "ABLATE" not in c and c not in prints:
+            if c not in prints:
                 prints[c] = fingerprint(P.k_view(K, pl))
     for c in cfgs:
         print(json.dumps({"cfg": c, "ms": [round(x, 4) for x in res[c]], "best_ms": round(min(res[c]), 4),
