@@ -35,8 +35,9 @@ class SparseGRFKernel(_Base):
 
     def _no_blocks(self, what: str):
         return NotImplementedError(
-            f"SparseGRFKernel.{what} needs step matrices: on a WalkPolynomial K and Phi are never formed; use "
-            "SparseGraphGP.predict and SparseGraphGP.marginal_log_likelihood, which run on the operator")
+            f"SparseGRFKernel.{what} needs step matrices: on a WalkPolynomial Phi is never formed; use "
+            "SparseGraphGP.predict and SparseGraphGP.marginal_log_likelihood, which run on the operator, and "
+            "SparseWalkOperatorKernel.forward or grf_amd.features.grf_kernel for K blocks and diagonals")
 
     def _step_set(self):
         """The StepMatrices of the kernel's step matrices, or its WalkPolynomial."""
@@ -58,3 +59,19 @@ class SparseGRFKernel(_Base):
         if self._operator() is not None:
             raise self._no_blocks("_get_feature_matrix")
         return feature_matrix(self.modulator_vector, self._step_set())
+
+
+class SparseWalkOperatorKernel(SparseGRFKernel):
+    """SparseGRFKernel on a ``WalkPolynomial`` (``step_matrices_torch=<WalkPolynomial>``): ``forward`` returns
+    blocks and diagonals of the exact K = p(G) p(G)^T from the operator itself (fp64 chains with the walk matrix,
+    the result in the modulator's dtype), differentiable in the modulator.  Phi is still never formed, so
+    ``_get_feature_matrix`` keeps raising."""
+
+    def __init__(self, max_walk_length, step_matrices_torch, **kwargs):
+        if not isinstance(step_matrices_torch, WalkPolynomial):
+            raise TypeError("SparseWalkOperatorKernel needs a WalkPolynomial (GraphPreprocessor.walk_operator())")
+        super().__init__(max_walk_length, step_matrices_torch, **kwargs)
+
+    def forward(self, x1_idx=None, x2_idx=None, diag=False, **params):
+        """K[x1, x2], or with ``diag`` (x1 and x2 the same tensor) diag K[x1]."""
+        return grf_kernel(self.modulator_vector, self.step_matrices, x1_idx, x2_idx, diag)

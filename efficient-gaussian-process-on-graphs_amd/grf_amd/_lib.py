@@ -166,6 +166,15 @@ SIGNATURES = {
     "grf_poly_grad_workspace_bytes": (_sz, [_i64, _i32]),
     "grf_poly_grad_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _sz,
                                  _vp]),
+    # K blocks, diagonals and their modulator gradients from the operator
+    "grf_poly_kernel_block_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "grf_poly_kernel_block_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp,
+                                         _i64, _vp, _sz, _vp]),
+    "grf_poly_kernel_diag_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "grf_poly_kernel_diag_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "grf_poly_kernel_grad_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "grf_poly_kernel_grad_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64,
+                                        _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

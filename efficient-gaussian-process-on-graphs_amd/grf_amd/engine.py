@@ -1303,6 +1303,101 @@ class GRFEngine:
                 "grf_poly_grad_f64")
         return out
 
+    # ------------------------------------- K blocks, diagonals and their gradients from the operator
+    def _nodes(self, x, n: int) -> torch.Tensor:
+        """The node indices of a kernel argument as int32 on the device (None: all n nodes)."""
+        if x is None:
+            return torch.arange(n, dtype=torch.int32, device=self.device)
+        return self._row_map(x)
+
+    def _poly_memory_guard(self, what: str, n1: int, n2: int, nbytes: int) -> None:
+        """ValueError before allocating when ``nbytes`` does not fit in free device memory (a driver query:
+        no device data is read and the stream is not waited for)."""
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if nbytes > free:
+            raise ValueError(f"{what}: the {n1} x {n2} block and its workspace need {int(nbytes)} bytes, more than "
+                             f"the {int(free)} bytes of free device memory")
+
+    def poly_kernel_block(self, op: WalkPolynomial, f, x1=None, x2=None) -> torch.Tensor:
+        """K[x1, x2] = S_1 p(G) p(G)^T S_2^T (fp64, len(x1) x len(x2); None: all nodes; indices may repeat) in
+        column blocks of 256 unit columns (grf_poly_kernel_block_f64).  Every column is bit-identical to
+        ``poly_gram_matvec`` on its unit vector."""
+        ft, n_f = self._poly_f(op, f)
+        n = op.shape[0]
+        r1, r2 = self._nodes(x1, n), self._nodes(x2, n)
+        n1, n2 = r1.numel(), r2.numel()
+        need = self.lib.grf_poly_kernel_block_workspace_bytes(n, n_f, n2)
+        self._poly_memory_guard("poly_kernel_block", n1, n2, n1 * n2 * 8 + need)
+        K = torch.empty((n1, n2), dtype=torch.float64, device=self.device)
+        ws = self._ws(need)
+        G, Gt = op.G, op.Gt
+        C.check(self.lib.grf_poly_kernel_block_f64(n, _p(G.ptr), _p(G.idx), _p(G.val), _p(Gt.ptr), _p(Gt.idx),
+                                                   _p(Gt.val), _p(ft), n_f, _p(r1), n1, _p(r2), n2, _p(K),
+                                                   max(n2, 1), _p(ws), ws.numel(), self.stream),
+                "grf_poly_kernel_block_f64")
+        return K
+
+    def poly_kernel_diag(self, op: WalkPolynomial, f, x=None) -> torch.Tensor:
+        """diag K[x] (fp64, len(x); None: all nodes) from the first chain alone (grf_poly_kernel_diag_f64)."""
+        ft, n_f = self._poly_f(op, f)
+        n = op.shape[0]
+        r = self._nodes(x, n)
+        n_x = r.numel()
+        need = self.lib.grf_poly_kernel_diag_workspace_bytes(n, n_f, n_x)
+        self._poly_memory_guard("poly_kernel_diag", n_x, 1, n_x * 8 + need)
+        out = self._empty(n_x, torch.float64)
+        ws = self._ws(need)
+        Gt = op.Gt
+        C.check(self.lib.grf_poly_kernel_diag_f64(n, _p(Gt.ptr), _p(Gt.idx), _p(Gt.val), _p(ft), n_f, _p(r), n_x,
+                                                  _p(out), _p(ws), ws.numel(), self.stream),
+                "grf_poly_kernel_diag_f64")
+        return out
+
+    def _merged_axis(self, r: torch.Tensor, n: int, g: torch.Tensor, dim: int):
+        """(inv, g'): inv[node] = one position of the node in r (or -1), and g with the slices of a node's repeated
+        positions along ``dim`` added into that one and the others zero.  No host read."""
+        pos = torch.arange(r.numel(), dtype=torch.int32, device=self.device)
+        inv = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+        inv[r.long()] = pos
+        return inv, torch.zeros_like(g).index_add_(dim, inv[r.long()].long(), g)
+
+    def poly_kernel_grad(self, op: WalkPolynomial, f, g: torch.Tensor, x1=None, x2=None,
+                         diag: bool = False) -> torch.Tensor:
+        """d<g, K[x1, x2]>/df_l (g: len(x1) x len(x2)) or, ``diag``, d<g, diag K[x1]>/df_l (g: len(x1)):
+        (n_f,) fp64 on the device (grf_poly_kernel_grad_f64).  Repeated indices are allowed."""
+        ft, n_f = self._poly_f(op, f)
+        n = op.shape[0]
+        r1 = self._nodes(x1, n)
+        n1 = r1.numel()
+        g = g.detach().to(self.device, torch.float64)
+        Gt = op.Gt
+        out = self._empty(n_f, torch.float64)
+        if diag:
+            g = g.flatten().contiguous()
+            if g.numel() != n1:
+                raise ValueError(f"poly_kernel_grad: g must hold one entry per node of x ({n1})")
+            need = self.lib.grf_poly_kernel_grad_workspace_bytes(n, n1, n1, 1)
+            self._poly_memory_guard("poly_kernel_grad", n1, 1, need)
+            ws = self._ws(need)
+            C.check(self.lib.grf_poly_kernel_grad_f64(n, _p(Gt.ptr), _p(Gt.idx), _p(Gt.val), _p(ft), n_f, _p(r1), n1,
+                                                      None, None, n1, None, _p(g), 1, 1, _p(out), _p(ws), ws.numel(),
+                                                      self.stream), "grf_poly_kernel_grad_f64")
+            return out
+        r2 = self._nodes(x2, n)
+        n2 = r2.numel()
+        if g.dim() != 2 or tuple(g.shape) != (n1, n2):
+            raise ValueError(f"poly_kernel_grad: g must be ({n1} x {n2})")
+        need = self.lib.grf_poly_kernel_grad_workspace_bytes(n, n1, n2, 0)
+        self._poly_memory_guard("poly_kernel_grad", n1, n2, 2 * n1 * n2 * 8 + need)
+        inv1, g = self._merged_axis(r1, n, g, 0)
+        inv2, g = self._merged_axis(r2, n, g, 1)
+        g = g.contiguous()
+        ws = self._ws(need)
+        C.check(self.lib.grf_poly_kernel_grad_f64(n, _p(Gt.ptr), _p(Gt.idx), _p(Gt.val), _p(ft), n_f, _p(r1), n1,
+                                                  _p(inv1), _p(r2), n2, _p(inv2), _p(g), max(n2, 1), 0, _p(out),
+                                                  _p(ws), ws.numel(), self.stream), "grf_poly_kernel_grad_f64")
+        return out
+
     @staticmethod
     def slq_logdet(coef: np.ndarray, iters: int, sq_norms: np.ndarray) -> float:
         """Stochastic Lanczos quadrature from CG coefficients: coef (2 max_iter x t) holds the probe columns'

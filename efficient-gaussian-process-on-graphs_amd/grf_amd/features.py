@@ -16,6 +16,9 @@ with the modulator gradient of ``K`` in ``backward`` (``GRFKernelFunction``):
     Z1 = Phi[x2]^T G^T,  Z2 = Phi[x1]^T G       # grf_csr_transpose + grf_spmm_csr, then grf_csr_rows_dot_cols
 
 Nothing here densifies Phi, and the step matrices never leave the device.
+
+On a ``WalkPolynomial`` (the exact Phi = sum_l f_l G^l, never formed) ``grf_kernel`` runs forward and backward on the
+operator's K-block entry points instead (``WalkOperatorKernelFunction``).
 """
 from __future__ import annotations
 
@@ -192,6 +195,14 @@ def _index(x: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
     return None if x is None else x.long().flatten().to(dev)
 
 
+def _same_rows(x1, x2, i1: Optional[torch.Tensor], i2: Optional[torch.Tensor]) -> bool:
+    """x1 and x2 are the same rows, decided without reading them back: both None, the same tensor, or views of
+    the same memory."""
+    return (x1 is None and x2 is None) or (x1 is x2) or (
+        i1 is not None and i2 is not None and i1.shape == i2.shape and i1.data_ptr() == i2.data_ptr()
+        and i1.stride() == i2.stride())
+
+
 class GRFKernelFunction(torch.autograd.Function):
     """K[x1, x2] (or its diagonal) = Phi(f)[x1] Phi(f)[x2]^T, differentiable w.r.t. the modulator f."""
 
@@ -204,9 +215,7 @@ class GRFKernelFunction(torch.autograd.Function):
         # x1 and x2 the same rows (the symmetric block): decided without reading the indices back -- the
         # same tensor, or views of the same memory (a K(x, x) call); equal values in two different tensors
         # take the general column-block path (the same numbers within the K tolerance)
-        same = (x1 is None and x2 is None) or (x1 is x2) or (
-            i1 is not None and i2 is not None and i1.shape == i2.shape and i1.data_ptr() == i2.data_ptr()
-            and i1.stride() == i2.stride())
+        same = _same_rows(x1, x2, i1, i2)
         phi = steps.phi(f)
         if diag:
             n1 = n if i1 is None else i1.numel()
@@ -251,8 +260,46 @@ class GRFKernelFunction(torch.autograd.Function):
         return grad.to(device=ctx.f_device, dtype=ctx.f_dtype), None, None, None, None
 
 
-def grf_kernel(f: torch.Tensor, steps: StepMatrices, x1=None, x2=None, diag: bool = False) -> torch.Tensor:
-    """K[x1, x2] = Phi[x1] Phi[x2]^T with Phi = sum_l f_l M_l (differentiable in f)."""
+class WalkOperatorKernelFunction(torch.autograd.Function):
+    """K[x1, x2] (or diag K[x]) of the exact kernel Phi = p(G) on a WalkPolynomial, differentiable w.r.t. the
+    modulator f: forward and backward run on the operator's K-block entry points in fp64 (GRFEngine.
+    poly_kernel_block / poly_kernel_diag / poly_kernel_grad), Phi never formed, nothing read back to the host."""
+
+    @staticmethod
+    def forward(ctx, f: torch.Tensor, op: WalkPolynomial, x1, x2, diag: bool):
+        eng = op.engine
+        i1, i2 = _index(x1, eng.device), _index(x2, eng.device)
+        if diag:
+            if not _same_rows(x1, x2, i1, i2):
+                raise ValueError("diag=True on a WalkPolynomial needs x1 and x2 to be the same tensor (diag K[x])")
+            out = eng.poly_kernel_diag(op, f, i1)
+        else:
+            out = eng.poly_kernel_block(op, f, i1, i2)
+            # (the two chains of K(x, x) round differently above and below the diagonal)
+            if i1 is None and i2 is None:
+                out = (out + out.t()).mul_(0.5)
+            else:
+                out = _square_symmetrised(out, i1, i2)
+        ctx.save_for_backward(f)
+        ctx.op, ctx.i1, ctx.i2, ctx.diag = op, i1, i2, diag
+        return out.to(f.dtype)
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor):
+        eng = ctx.op.engine
+        f, = ctx.saved_tensors
+        grad = torch.zeros(f.numel(), dtype=torch.float64, device=eng.device)
+        out = eng.poly_kernel_grad(ctx.op, f, g, ctx.i1, ctx.i2, ctx.diag)
+        grad[:out.numel()] = out  # (entries of f past the walk length do not enter)
+        # (on f's own device: a modulator parameter left on the CPU still gets its gradient)
+        return grad.to(device=f.device, dtype=f.dtype), None, None, None, None
+
+
+def grf_kernel(f: torch.Tensor, steps, x1=None, x2=None, diag: bool = False) -> torch.Tensor:
+    """K[x1, x2] = Phi[x1] Phi[x2]^T, differentiable in f, with Phi = sum_l f_l M_l on a StepMatrices or the
+    exact Phi = sum_l f_l G^l on a WalkPolynomial (matrix-free, fp64 arithmetic, the result in f's dtype)."""
+    if isinstance(steps, WalkPolynomial):
+        return WalkOperatorKernelFunction.apply(f, steps, x1, x2, diag)
     return GRFKernelFunction.apply(f, steps, x1, x2, diag)
 
 

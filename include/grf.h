@@ -747,6 +747,59 @@ int32_t grf_poly_grad_f64(int64_t n, const int64_t *gt_ptr, const int32_t *gt_id
                           const double *B, int64_t ld, const double *wt, int32_t n_rhs, double *out, void *workspace,
                           size_t workspace_bytes, grf_stream_t stream);
 
+/* K blocks, diagonals and their modulator gradients from the operator (the K = Phi[x1] Phi[x2]^T of
+ * general_kernel_pofm.py:45-96 where Phi cannot be formed).  With Psi_i = p(G^T) S_i^T (n x n_i, S_i selecting
+ * the nodes x_i, which may repeat and need not be sorted: an entry of x_i is just a column),
+ *     K[x1, x2] = Psi_1^T Psi_2 = S_1 p(G) p(G)^T S_2^T,     diag K[x]_c = sum_r Psi[r, c]^2.
+ * x1, x2, x: int32 node indices on the device.  Columns are processed in blocks of at most 256; every step
+ * follows the order rule above, unchanged.
+ *
+ * Unit columns.  Chain 1 runs on the unit columns e_{x2[c]} without reading a block: the value gathered at
+ * node j, column c, is RN(f_{n_f-1} * 1) if j == x2[c], else +0.0, and the f_l X addend is fma(f_l, [row == x2[c]],
+ * sum).  Column c of the block is therefore bit-identical to grf_poly_apply_f64 (G^T, then G on the rows x1)
+ * applied to e_{x2[c]}.
+ *
+ * grf_poly_kernel_block_f64: K (n1 x n2 into a row-major block, ldk >= n2; nothing outside it is written).  Per
+ * column block chain 1 with G^T from the unit columns, then chain 2 with G whose last step runs on the rows x1
+ * only and writes into K at the block's column offset.  n_f = 1: f_0^2 [x1[r] == x2[c]], no matrix read.
+ * n1 = 0 or n2 = 0: nothing is touched.  Workspace: grf_poly_kernel_block_workspace_bytes(n, n_f, n2) (one
+ * n x min(n2, 256) block, three for n_f > 2). */
+size_t grf_poly_kernel_block_workspace_bytes(int64_t n, int32_t n_f, int64_t n2);
+int32_t grf_poly_kernel_block_f64(int64_t n, const int64_t *g_ptr, const int32_t *g_idx, const double *g_val,
+                                  const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val, const double *f,
+                                  int32_t n_f, const int32_t *x1, int64_t n1, const int32_t *x2, int64_t n2, double *K,
+                                  int64_t ldk, void *workspace, size_t workspace_bytes, grf_stream_t stream);
+
+/* diag K[x] (n_x doubles): chain 1 only; its last step computes Psi[r, :] by the order rule and adds
+ * fma(Psi[r, c], Psi[r, c], sum) per column without writing Psi: a wave's rows ascending, the 4 waves in order,
+ * one fp64 partial per (block, column), the last block (by the ticket at the workspace's start, zero again
+ * afterwards) adds a column's partials in block order.  n_f = 1: RN(f_0^2).  Workspace:
+ * grf_poly_kernel_diag_workspace_bytes(n, n_f, n_x). */
+size_t grf_poly_kernel_diag_workspace_bytes(int64_t n, int32_t n_f, int64_t n_x);
+int32_t grf_poly_kernel_diag_f64(int64_t n, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
+                                 const double *f, int32_t n_f, const int32_t *x, int64_t n_x, double *out,
+                                 void *workspace, size_t workspace_bytes, grf_stream_t stream);
+
+/* The modulator gradient of <g, K[x1, x2]> (diag = 0; g: n1 x n2, ldg >= n2) or of <g, diag K[x1]> (diag != 0;
+ * g: n1 doubles; x2, inv1, inv2, ldg unused):
+ *     out[l] = sum_c <((G^T)^l S_1^T g)[:, c], Psi_2[:, c]> + sum_r <((G^T)^l S_2^T g^T)[:, r], Psi_1[:, r]>,
+ *     out[l] = 2 sum_c g_c <(G^T)^l e_{x_c}, Psi[:, c]>                                     (diagonal),  l < n_f.
+ * inv1 / inv2 (int32 [n]): a node's row / column of g, or -1; S_i^T g is read through them and never stored.  A
+ * node that x_i repeats has one row (column) there: the caller adds its repeats' cotangents into it and zeroes
+ * the others, which leaves the sum unchanged.  Per column block Psi comes from chain 1 on the unit columns;
+ * each Krylov step U_l = G^T U_{l-1} (order rule steps 1-2) is fused with fma(U, Psi, sum) over a node's
+ * columns c = lane, lane + 64, ..., reduced as in grf_poly_grad_f64; the column blocks' contributions are added
+ * in block order, the first half before the mirrored one (which reads g^T from a transposed copy in the
+ * workspace).  The diagonal form starts from U_0 = [g_c e_{x_c}]_c, read from no block, and scales each block's
+ * sum by 2.  An empty block gives zeros.  out: n_f doubles on the device.  Workspace:
+ * grf_poly_kernel_grad_workspace_bytes(n, n1, n2, diag) (three n x min(max(n1, n2), 256) blocks and n1 x n2). */
+size_t grf_poly_kernel_grad_workspace_bytes(int64_t n, int64_t n1, int64_t n2, int32_t diag);
+int32_t grf_poly_kernel_grad_f64(int64_t n, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
+                                 const double *f, int32_t n_f, const int32_t *x1, int64_t n1, const int32_t *inv1,
+                                 const int32_t *x2, int64_t n2, const int32_t *inv2, const double *g, int64_t ldg,
+                                 int32_t diag, double *out, void *workspace, size_t workspace_bytes,
+                                 grf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

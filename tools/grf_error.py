@@ -6,6 +6,10 @@ exact step matrices (GRFEngine.exact_steps); the GRF K from the Philox walks at 
 benchmarked fused path where m L <= 4096, the walk / features path above).  Printed per walks-per-node value:
 ||K_grf - K_exact||_F / ||K_exact||_F, mean and spread over --seeds walk seeds -- the paper's figure of merit.
 Both K are formed in fp64 from the fp64 features (dense: keep the graph at ~10^4 nodes).  One JSON line at the end.
+
+--operator takes the exact K from the walk operator instead (GRFEngine.poly_kernel_block on a WalkPolynomial:
+Horner chains with L itself, no power of it formed), so the tool also runs on graphs whose exact step matrices
+fill in -- Erdos-Renyi graphs, where exact_steps raises.
 """
 import argparse
 import json
@@ -60,11 +64,13 @@ def main():
     ap.add_argument("--p-halt", type=float, default=0.1)
     ap.add_argument("--beta", type=float, default=1.0, help="diffusion modulator (-beta/2)^l / l!")
     ap.add_argument("--seeds", type=int, default=3)
+    ap.add_argument("--operator", action="store_true",
+                    help="the exact K from the walk operator (no step matrices: works where they fill in)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("grf_error: no GPU")
     from grf_amd import _lib as C
-    from grf_amd.engine import get_engine
+    from grf_amd.engine import WalkPolynomial, get_engine
     from grf_amd.graphs import er_graph_exact_edges
 
     kind, _, spec = args.graph.partition(":")
@@ -82,13 +88,19 @@ def main():
     L = args.length
     f = np.array([(-args.beta / 2.0) ** l / math.factorial(l) for l in range(L)])
     G = eng.laplacian(A)
-    steps = eng.exact_steps(G, L)
-    Phi = sum(fl * dense64(eng, M) for fl, M in zip(f, steps))
-    K = Phi @ Phi.T
+    out = {"graph": args.graph, "n": A.shape[0], "L": L, "p_halt": args.p_halt, "beta": args.beta, "rows": []}
+    if args.operator:
+        K = eng.poly_kernel_block(WalkPolynomial(G, L, engine=eng), torch.from_numpy(f))
+        out["exact_from"] = "operator"
+        what = f"exact K from the operator, nnz(L) = {G.nnz}"
+    else:
+        steps = eng.exact_steps(G, L)
+        Phi = sum(fl * dense64(eng, M) for fl, M in zip(f, steps))
+        K = Phi @ Phi.T
+        out["nnz_exact_steps"] = [M.nnz for M in steps]
+        what = f"exact steps nnz = {out['nnz_exact_steps']}"
     k_norm = float(torch.linalg.norm(K))
-    out = {"graph": args.graph, "n": A.shape[0], "L": L, "p_halt": args.p_halt, "beta": args.beta,
-           "nnz_exact_steps": [M.nnz for M in steps], "rows": []}
-    print(f"{args.graph}: n = {A.shape[0]}, exact steps nnz = {out['nnz_exact_steps']}, ||K||_F = {k_norm:.6g}")
+    print(f"{args.graph}: n = {A.shape[0]}, {what}, ||K||_F = {k_norm:.6g}")
     print(f"{'walks':>8} {'rel Frobenius error':>22} {'[min, max]':>26}")
     for m in (int(x) for x in args.walks.split(",")):
         errs = []
