@@ -4,8 +4,9 @@ GPflow / TensorFlow are not installed in this image, so the two fast-GRF kernels
 are provided with the same constructor and ``K`` / ``K_diag`` / ``grf_kernel`` API
 backed by the GPU engine (numpy in, numpy out), and so are the two exact walk-power
 (PoFM) kernels they estimate, on the device SpGEMM's exact step matrices.  The
-eigendecomposition / TF-walker kernels of the reference are outside the GRF hot path and
-raise NotImplementedError.
+package-level names GraphDiffusionKernel and GraphDiffusionGRFKernel raise NotImplementedError;
+the closed-form kernel sigma_f^2 exp(-beta L) is in the submodule ``diffusion_kernel_exact``
+(the reference's module path), the TF-walker kernel is outside the GRF hot path.
 """
 from .diffusion_kernel_fast_grf import GraphDiffusionFastGRFKernel
 from .diffusion_kernel_pofm import GraphDiffusionPoFMKernel

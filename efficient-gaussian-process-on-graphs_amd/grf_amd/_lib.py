@@ -175,6 +175,13 @@ SIGNATURES = {
     "grf_poly_kernel_grad_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
     "grf_poly_kernel_grad_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64,
                                         _i32, _vp, _vp, _sz, _vp]),
+    # the exact diffusion kernel exp(-beta L): the dense fp64 NT product on the matrix cores and its driver
+    "grf_gemm_nt_f64_workspace_bytes": (_sz, [_i64, _i64]),
+    "grf_gemm_nt_f64": (_i32, [_i64, _i64, _i64, _dbl, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _dbl, _vp, _i64,
+                               _dbl, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "grf_expm_squarings": (_i32, [_dbl]),
+    "grf_expm_sym_f64_workspace_bytes": (_sz, [_i64]),
+    "grf_expm_sym_f64": (_i32, [_i64, _vp, _i64, _dbl, _dbl, _vp, _i64, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -246,3 +246,29 @@ def gram_from_features(F: np.ndarray, f: Sequence[float], device=None) -> np.nda
         raise ValueError("modulator length must equal the step tensor's last dimension")
     from .features import DenseSteps
     return DenseSteps(F, eng).gram(torch.from_numpy(f)).cpu().numpy().astype(np.float64)
+
+
+# ------------------------------------------------------- the exact diffusion kernel exp(-beta L)
+def dense_laplacian_device(adj_matrix, normalize_laplacian: bool = True, device=None):
+    """(L, radius): the dense fp64 Laplacian on the device (grf_laplacian_dense: LAP_NUMPY_SAFE, which leaves a
+    degree-0 node the row e_i as graph_kernels/utils.py:22-26 does, or the combinatorial D - W) and a bound on its
+    spectral radius -- 2 for a normalised Laplacian of non-negative weights, else ||L||_inf, computed on the
+    device and read once."""
+    W = np.asarray(adj_matrix, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] != W.shape[1]:
+        raise ValueError("Adjacency matrix must be square.")
+    eng = get_engine(device)
+    L = eng.laplacian_dense_matrix(W, C.LAP_NUMPY_SAFE if normalize_laplacian else C.LAP_COMBINATORIAL)
+    if normalize_laplacian and not (W < 0).any():
+        radius = 2.0
+    else:
+        radius = float(L.abs().sum(dim=1).max().item())
+    return L, radius
+
+
+def diffusion_kernel_exact(adj_matrix, beta=2.0, *, normalize_laplacian: bool = True, device=None) -> np.ndarray:
+    """diffusion_kernel(adj_matrix, beta) (graph_kernels/diffusion_kernel.py:6-12): the whole exp(-beta L) as
+    fp64 numpy, by scaling and squaring on the fp64 matrix cores (GRFEngine.diffusion_expm)."""
+    beta = float(beta)
+    L, radius = dense_laplacian_device(adj_matrix, normalize_laplacian, device)
+    return get_engine(device).diffusion_expm(L, beta, beta * radius).cpu().numpy()

@@ -1398,6 +1398,116 @@ class GRFEngine:
                                                   _p(ws), ws.numel(), self.stream), "grf_poly_kernel_grad_f64")
         return out
 
+    # ------------------------------------- the exact diffusion kernel exp(-beta L) on the fp64 matrix cores
+    def _dense_f64(self, M: torch.Tensor, what: str) -> torch.Tensor:
+        """A 2-D fp64 device matrix whose rows are contiguous (any row pitch), copied only if it is not one."""
+        if not torch.is_tensor(M) or M.dim() != 2:
+            raise ValueError(f"{what} must be a 2-D tensor")
+        if M.dtype != torch.float64 or M.device != self.device:
+            M = M.to(self.device, torch.float64)
+        if M.shape[1] > 1 and M.stride(1) != 1 or (M.shape[0] > 1 and M.stride(0) < M.shape[1]):
+            M = M.contiguous()
+        return M
+
+    @staticmethod
+    def _pitch(M: torch.Tensor) -> int:
+        return int(M.stride(0)) if M.shape[0] > 1 else max(int(M.shape[1]), 1)
+
+    def _checked_rows(self, r, n_rows: int, what: str) -> Optional[torch.Tensor]:
+        """An int32 row map on the device, its entries checked against the operand's rows (one host read)."""
+        if r is None:
+            return None
+        r = self._row_map(r)
+        if r.numel() and not bool(((r >= 0) & (r < n_rows)).all()):
+            raise ValueError(f"{what}: row indices must lie in [0, {n_rows})")
+        return r
+
+    def _dense_memory_guard(self, what: str, n: int, nbytes: int) -> None:
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if nbytes > free:
+            raise ValueError(f"{what}: n = {n} needs {int(nbytes)} bytes for its result and workspace, more than the "
+                             f"{int(free)} bytes of free device memory")
+
+    def gemm_nt_f64(self, A: Optional[torch.Tensor], B: Optional[torch.Tensor], *, alpha: float = 1.0, ra=None,
+                    rb=None, gamma: float = 1.0, Z: Optional[torch.Tensor] = None, delta: float = 0.0,
+                    out: Optional[torch.Tensor] = None, symmetric: bool = False,
+                    W: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """C = alpha A[ra] B[rb]^T + gamma Z + delta I in fp64 on the matrix cores (grf_gemm_nt_f64): A (rows x nk)
+        and B (rows x nk) are read by rows through the optional row maps; ``out`` (n1 x n2, may be ``Z``) receives
+        C and is returned.  ``symmetric``: the caller promises a symmetric result; the upper tiles are computed
+        and mirrored, so C is bitwise symmetric.  ``W`` (n1 x n2): nothing is written and sum_ij W_ij C_ij comes
+        back as a one-element fp64 device tensor.  A = B = None: C = gamma Z + delta I."""
+        if (A is None) != (B is None):
+            raise ValueError("gemm_nt_f64: A and B go together")
+        if A is not None:
+            A, B = self._dense_f64(A, "gemm_nt_f64: A"), self._dense_f64(B, "gemm_nt_f64: B")
+            if A.shape[1] != B.shape[1]:
+                raise ValueError(f"gemm_nt_f64: A has {A.shape[1]} columns, B {B.shape[1]}")
+            nk = int(A.shape[1])
+            ra = self._checked_rows(ra, A.shape[0], "gemm_nt_f64: ra")
+            rb = self._checked_rows(rb, B.shape[0], "gemm_nt_f64: rb")
+            n1 = int(A.shape[0]) if ra is None else ra.numel()
+            n2 = int(B.shape[0]) if rb is None else rb.numel()
+        else:
+            ref = Z if Z is not None else (out if out is not None else W)
+            if ref is None or ra is not None or rb is not None:
+                raise ValueError("gemm_nt_f64: without operands the shape comes from Z, out or W (and no row maps)")
+            nk, (n1, n2) = 0, (int(ref.shape[0]), int(ref.shape[1]))
+        for name, M in (("Z", Z), ("out", out), ("W", W)):
+            if M is not None and (M.dim() != 2 or tuple(M.shape) != (n1, n2)):
+                raise ValueError(f"gemm_nt_f64: {name} must be ({n1} x {n2})")
+        if Z is not None:
+            Z = Z if Z is out else self._dense_f64(Z, "gemm_nt_f64: Z")
+        contract = W is not None
+        need = self.lib.grf_gemm_nt_f64_workspace_bytes(n1, n2) if contract else 0
+        if contract:
+            W = self._dense_f64(W, "gemm_nt_f64: W")
+            self._dense_memory_guard("gemm_nt_f64", max(n1, n2), need)
+            res = torch.zeros(1, dtype=torch.float64, device=self.device)
+        else:
+            if out is None:
+                self._dense_memory_guard("gemm_nt_f64", max(n1, n2), n1 * n2 * 8)
+                out = torch.empty((n1, n2), dtype=torch.float64, device=self.device)
+            elif out.dtype != torch.float64 or out.device != self.device or (n2 > 1 and out.stride(1) != 1):
+                raise ValueError("gemm_nt_f64: out must be an fp64 tensor on this device with contiguous rows")
+            res = out
+        ws = self._ws(need) if contract else None
+        C.check(self.lib.grf_gemm_nt_f64(
+            n1, n2, nk, float(alpha), _p(A), self._pitch(A) if nk else 0, int(A.shape[0]) if nk else 0, _p(ra),
+            _p(B), self._pitch(B) if nk else 0, int(B.shape[0]) if nk else 0, _p(rb), float(gamma), _p(Z),
+            self._pitch(Z) if Z is not None else 0, float(delta), None if contract else _p(out),
+            0 if contract else self._pitch(out), int(bool(symmetric)), _p(W), self._pitch(W) if contract else 0,
+            _p(res) if contract else None, _p(ws), ws.numel() if contract else 0, self.stream), "grf_gemm_nt_f64")
+        return res
+
+    def expm_squarings(self, rho: float) -> int:
+        """s = max(0, ceil(log2 rho)) of grf_expm_sym_f64 (its product count is 17 + s)."""
+        return int(self.lib.grf_expm_squarings(float(rho)))
+
+    def diffusion_expm(self, L_dev: torch.Tensor, beta: float, rho: float) -> torch.Tensor:
+        """E = exp(-beta L) (fp64, n x n, bitwise symmetric) of a dense symmetric ``L_dev`` on the device by scaling
+        and squaring (grf_expm_sym_f64); ``rho`` bounds the spectral radius of beta L.  No host read."""
+        L_dev = self._dense_f64(L_dev, "diffusion_expm: L")
+        n = int(L_dev.shape[0])
+        if L_dev.shape[1] != n or n < 1:
+            raise ValueError("diffusion_expm: L must be square and non-empty")
+        need = self.lib.grf_expm_sym_f64_workspace_bytes(n)
+        self._dense_memory_guard("diffusion_expm", n, n * n * 8 + need)
+        E = torch.empty((n, n), dtype=torch.float64, device=self.device)
+        ws = self._ws(need)
+        C.check(self.lib.grf_expm_sym_f64(n, _p(L_dev), self._pitch(L_dev), float(beta), float(rho), _p(E), n, _p(ws),
+                                          ws.numel(), self.stream), "grf_expm_sym_f64")
+        return E
+
+    def laplacian_dense_matrix(self, W, mode: int) -> torch.Tensor:
+        """The Laplacian of grf_laplacian_dense as a dense fp64 n x n device matrix."""
+        G = self.walk_matrix_dense(W, mode)
+        n, nnz = G.n_rows, G.nnz
+        L = torch.zeros((n, n), dtype=torch.float64, device=self.device)
+        r = torch.repeat_interleave(torch.arange(n, device=self.device), G.ptr[1:] - G.ptr[:-1], output_size=nnz)
+        L[r, G.idx[:nnz].long()] = G.val[:nnz]
+        return L
+
     @staticmethod
     def slq_logdet(coef: np.ndarray, iters: int, sq_norms: np.ndarray) -> float:
         """Stochastic Lanczos quadrature from CG coefficients: coef (2 max_iter x t) holds the probe columns'

@@ -800,6 +800,63 @@ int32_t grf_poly_kernel_grad_f64(int64_t n, const int64_t *gt_ptr, const int32_t
                                  int32_t diag, double *out, void *workspace, size_t workspace_bytes,
                                  grf_stream_t stream);
 
+/* ------------------------------------------- the exact diffusion kernel exp(-beta L) on the fp64 matrix cores
+ * Replaces efficient_graph_gp/graph_kernels/diffusion_kernel.py:6-12 (scipy.linalg.expm of -beta L) and the
+ * kernel matrix of efficient_graph_gp/gpflow_kernels/diffusion_kernel_exact.py:6-46 (tf.linalg.expm).  Purely
+ * additive to ABI 9.
+ *
+ * grf_gemm_nt_f64: a dense fp64 product on v_mfma_f64_16x16x4_f64,
+ *     C[i, j] = alpha * sum_k A[ra(i), k] B[rb(j), k] + gamma * Z[i, j] + delta * [i == j],  i < n1, j < n2, k < nk.
+ * Both operands are read by rows; lda, ldb >= nk, ldc, ldz, ldw >= n2.  ra / rb: optional int32 row maps (NULL:
+ * identity; repeated and unsorted indices are just rows); a_rows / b_rows: the rows A / B hold (n1 / n2 without
+ * a map), used for the overlap check only -- a map's entries must lie in [0, rows).  Z optional (NULL: no addend,
+ * gamma unused); Z may alias C exactly (same pointer and pitch).  C must overlap neither A nor B.
+ *
+ * Order rule of an entry (fp64 throughout, no split-k, no floating-point atomics: two calls give the same bits):
+ *   1. acc starts from +0.0; the k-tiles of 16 are added in ascending order, within a k-tile its four groups
+ *      of 4 consecutive k in ascending order, each group by one v_mfma_f64_16x16x4_f64 onto acc (k >= nk reads
+ *      +0.0); one accumulator chain per entry, the same in every mode;
+ *   2. c = RN(alpha * acc);  3. with Z: c = RN(c + RN(gamma * Z[i, j]));  4. if i == j: c = RN(c + delta).
+ * Modes:
+ *   general      (symmetric = 0, W = NULL) every 128 x 128 tile is computed and written.
+ *   symmetric    (symmetric != 0) needs n1 == n2, no row maps, W = NULL, and the caller's promise that the product
+ *                and Z are symmetric.  Only tiles with bj >= bi are computed; an entry j >= i is written to C[i, j]
+ *                and C[j, i] from the same accumulator (Z is read at [i, j], j >= i, only), so C is bitwise
+ *                symmetric even when A != B, and its upper triangle equals the general mode's bit for bit.
+ *   contraction  (W != NULL) out[0] = sum_ij W[i, j] c_ij on the device; C is not read or written (may be NULL).
+ *                A lane adds its 64 entries of the tile by fma(W, c, sum) in a fixed order, the 64 lanes by an
+ *                xor tree, the 4 waves in order, one fp64 partial per tile; the last tile (by a ticket at the
+ *                workspace's start, zero again afterwards) adds the partials in tile order.  Summation depth
+ *                beyond the product's nk: 64 + 6 + 3 + tiles.  Workspace: grf_gemm_nt_f64_workspace_bytes(n1, n2)
+ *                (other modes need none).
+ * Columns [n2, ldc) of C and everything past the buffer are never written; GRF_EINVAL writes nothing; n1 == 0 or
+ * n2 == 0 touches nothing; nk == 0 gives gamma Z + delta I (A, B unused). */
+size_t grf_gemm_nt_f64_workspace_bytes(int64_t n1, int64_t n2);
+int32_t grf_gemm_nt_f64(int64_t n1, int64_t n2, int64_t nk, double alpha, const double *A, int64_t lda,
+                        int64_t a_rows, const int32_t *ra, const double *B, int64_t ldb, int64_t b_rows,
+                        const int32_t *rb, double gamma, const double *Z, int64_t ldz, double delta, double *C,
+                        int64_t ldc, int32_t symmetric, const double *W, int64_t ldw, double *out, void *workspace,
+                        size_t workspace_bytes, grf_stream_t stream);
+
+/* grf_expm_sym_f64: E = exp(-beta L) for a dense symmetric L (n x n, ldl >= n) on the device, by scaling and
+ * squaring; a host-side chain of grf_gemm_nt_f64 calls, no host read of device data.  rho: the caller's bound on
+ * the spectral radius of beta L (2 beta for a normalised Laplacian of non-negative weights, beta ||L||_inf
+ * otherwise).
+ * Order rule (17 + s products):
+ *   1. s = grf_expm_squarings(rho) = max(0, ceil(log2 rho)) (theta = 1: ||X||_2 <= 1, Taylor remainder <= 1 / 19!);
+ *   2. X = RN(-beta 2^-s * L) entry by entry (the factor itself is exact);
+ *   3. Horner on the degree-18 Taylor polynomial: H_18 = RN(RN(RN(1/18) X) + I), then for k = 17 .. 1
+ *      H_k = I + RN(1/k) (X H_{k+1}) by one symmetric-mode product (alpha = RN(1/k), delta = 1): 17 products;
+ *   4. s squarings P <- P P (symmetric mode, alpha = 1) between two ping-pong buffers; the last product of all
+ *      is written to E.  Every intermediate has its spectrum in (0, 1]: nothing overflows for any beta > 0.
+ * E (lde >= n) is bitwise symmetric; n = 1 works.  beta <= 0, a non-finite beta or rho, or a rho that needs more
+ * than 64 squarings: GRF_EINVAL.  E, L and the workspace must not overlap.  Workspace:
+ * grf_expm_sym_f64_workspace_bytes(n) (three n x n blocks, rows padded to an even length). */
+int32_t grf_expm_squarings(double rho);
+size_t grf_expm_sym_f64_workspace_bytes(int64_t n);
+int32_t grf_expm_sym_f64(int64_t n, const double *L, int64_t ldl, double beta, double rho, double *E, int64_t lde,
+                         void *workspace, size_t workspace_bytes, grf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

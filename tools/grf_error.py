@@ -10,6 +10,11 @@ Both K are formed in fp64 from the fp64 features (dense: keep the graph at ~10^4
 --operator takes the exact K from the walk operator instead (GRFEngine.poly_kernel_block on a WalkPolynomial:
 Horner chains with L itself, no power of it formed), so the tool also runs on graphs whose exact step matrices
 fill in -- Erdos-Renyi graphs, where exact_steps raises.
+
+--truth expm measures against the closed form exp(-beta L) instead (GRFEngine.diffusion_expm: scaling and squaring
+on the fp64 matrix cores) and splits the GRF kernel's error in two: the truncation error of the walk-power series
+(the exact walk-power K against exp(-beta L), independent of the walks) and the Monte-Carlo error (the GRF K against
+the walk-power K); the total is the GRF K against exp(-beta L).  All three relative to ||exp(-beta L)||_F.
 """
 import argparse
 import json
@@ -66,6 +71,9 @@ def main():
     ap.add_argument("--seeds", type=int, default=3)
     ap.add_argument("--operator", action="store_true",
                     help="the exact K from the walk operator (no step matrices: works where they fill in)")
+    ap.add_argument("--truth", choices=("pofm", "expm"), default="pofm",
+                    help="pofm: against the exact walk-power K; expm: against exp(-beta L), truncation and "
+                         "Monte-Carlo error apart")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("grf_error: no GPU")
@@ -101,9 +109,22 @@ def main():
         what = f"exact steps nnz = {out['nnz_exact_steps']}"
     k_norm = float(torch.linalg.norm(K))
     print(f"{args.graph}: n = {A.shape[0]}, {what}, ||K||_F = {k_norm:.6g}")
-    print(f"{'walks':>8} {'rel Frobenius error':>22} {'[min, max]':>26}")
+    E = None
+    if args.truth == "expm":
+        # the scipy-semantics normalised Laplacian of non-negative weights: spectrum in [0, 2]
+        rho = 2.0 * args.beta
+        E = eng.diffusion_expm(dense64(eng, G), args.beta, rho)
+        e_norm = float(torch.linalg.norm(E))
+        out["truth"] = "expm"
+        out["expm_products"] = 17 + eng.expm_squarings(rho)
+        out["truncation"] = float(torch.linalg.norm(K - E)) / e_norm
+        print(f"exp(-beta L): {out['expm_products']} dense products, ||E||_F = {e_norm:.6g}; truncation error "
+              f"||K_pofm - E||_F / ||E||_F = {out['truncation']:.4e}")
+        print(f"{'walks':>8} {'total (vs expm)':>18} {'Monte-Carlo (vs pofm)':>24} {'truncation':>14}")
+    else:
+        print(f"{'walks':>8} {'rel Frobenius error':>22} {'[min, max]':>26}")
     for m in (int(x) for x in args.walks.split(",")):
-        errs = []
+        errs, totals = [], []
         for seed in range(args.seeds):
             if m * L <= 4096:
                 rows = eng.walk_phi(G, m, args.p_halt, L, f, seed=100 + seed, norm=C.NORM_MUL_RECIP)
@@ -111,8 +132,16 @@ def main():
                 slots = eng.walk(G, m, args.p_halt, L, rng=C.RNG_PHILOX, seed=100 + seed)
                 rows = eng.features(slots, f, C.NORM_MUL_RECIP)
             P = dense64(eng, eng.compact(rows))
-            errs.append(float(torch.linalg.norm(P @ P.T - K)) / k_norm)
-            del P, rows
+            Kg = P @ P.T
+            errs.append(float(torch.linalg.norm(Kg - K)) / (k_norm if E is None else e_norm))
+            if E is not None:
+                totals.append(float(torch.linalg.norm(Kg - E)) / e_norm)
+            del P, rows, Kg
+        if E is not None:
+            out["rows"].append({"walks": m, "total": float(np.mean(totals)), "monte_carlo": float(np.mean(errs)),
+                                "truncation": out["truncation"], "total_min": min(totals), "total_max": max(totals)})
+            print(f"{m:>8} {np.mean(totals):>18.4e} {np.mean(errs):>24.4e} {out['truncation']:>14.4e}", flush=True)
+            continue
         out["rows"].append({"walks": m, "mean": float(np.mean(errs)), "min": min(errs), "max": max(errs)})
         print(f"{m:>8} {np.mean(errs):>22.4e} {'[%.4e, %.4e]' % (min(errs), max(errs)):>26}", flush=True)
     print(json.dumps(out))
