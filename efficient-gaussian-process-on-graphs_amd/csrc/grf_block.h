@@ -36,6 +36,13 @@ __device__ inline T wave_sum(T v) {
     return v;
 }
 
+// the maximum over the wave's 64 lanes, in every lane
+__device__ inline float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
 // Exclusive scan over the whole workgroup (blockDim.x multiple of 64, <= 1024).
 // `scratch` must hold blockDim.x/64 + 1 elements of T.  Returns the exclusive
 // prefix of this thread; *total receives the workgroup sum.  Contains barriers.

@@ -132,10 +132,26 @@ size_t scan_ws_bytes(int64_t n) { return scan_ws_elems(n) * sizeof(int64_t); }
 constexpr int kCompactRows = 4, kCompactU = 2;
 static_assert(kCompactRows == 4, "wg_max holds one max per 4 rows (grf_phi_row_shifts_stats reads cdiv(n, 4))");
 
-// kStats: also the Gram row-shift statistics of the compact rows (row max / fp64 sum of |value| and
-// the max of every kCompactRows rows): the entries of a row are summed in the order
-// phi_row_stats_kernel reads them (lane + 64 i, then the wave sum), so grf_phi_row_shifts_stats gives
-// grf_phi_row_shifts' bits without another pass over the values
+// The Gram row-shift statistics of one row held by one wave: max |v| and the fp64 sum of |v|.  Every
+// kernel that takes them (the compaction, the atomic fill, the binning pass, phi_row_stats_kernel) adds
+// the row's elements lane + 64 i to its lane in ascending i and reduces with wave_sum, so all of them
+// give the same row_sum bits and hence the same shifts.
+struct RowStats {
+    float mx = 0.f;
+    double sm = 0.0;
+    __device__ void add(float v) {
+        const float a = fabsf(v);
+        mx = fmaxf(mx, a);
+        sm += (double)a;
+    }
+    __device__ void reduce() {  // (every lane then holds the row's figures)
+        mx = wave_max(mx);
+        sm = wave_sum<double>(sm);
+    }
+};
+
+// kStats: also the row statistics of the compact rows and the max of every kCompactRows rows, so
+// grf_phi_row_shifts_stats gives grf_phi_row_shifts' bits without another pass over the values
 template <bool kStats>
 __global__ __launch_bounds__(256) void compact_rows_kernel(int64_t n_rows, int64_t cap, const int32_t *__restrict__ cnt,
                                                            const int64_t *__restrict__ out_ptr,
@@ -159,13 +175,7 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(int64_t n_rows, int64
         src[r] = (row0 + r) * cap;
         cmax = c[r] > cmax ? c[r] : cmax;
     }
-    float mx[kCompactRows];
-    double sm[kCompactRows];
-#pragma unroll
-    for (int r = 0; r < kCompactRows; ++r) {
-        mx[r] = 0.f;
-        sm[r] = 0.0;
-    }
+    RowStats stats[kCompactRows];
     for (int64_t base = lane; base < cmax; base += 64 * kCompactU) {
         int32_t ix[kCompactRows][kCompactU];
         float v32[kCompactRows][kCompactU];
@@ -189,26 +199,19 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(int64_t n_rows, int64
                 out_idx[dst[r] + e] = ix[r][u];
                 if (out_val) out_val[dst[r] + e] = v64[r][u];
                 if (out_val32) out_val32[dst[r] + e] = v32[r][u];
-                if (kStats) {
-                    const float a = fabsf(v32[r][u]);
-                    mx[r] = fmaxf(mx[r], a);
-                    sm[r] += (double)a;
-                }
+                if (kStats) stats[r].add(v32[r][u]);
             }
     }
     if (!kStats) return;
     float gmx = 0.f;
 #pragma unroll
     for (int r = 0; r < kCompactRows; ++r) {
-        float m = mx[r];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-        const double s = wave_sum<double>(sm[r]);
+        stats[r].reduce();
         if (lane == 0 && row0 + r < n_rows) {
-            row_max[row0 + r] = m;
-            row_sum[row0 + r] = s;
+            row_max[row0 + r] = stats[r].mx;
+            row_sum[row0 + r] = stats[r].sm;
         }
-        gmx = fmaxf(gmx, m);
+        gmx = fmaxf(gmx, stats[r].mx);
     }
     if (lane == 0) wg_max[gw] = gmx;
 }
@@ -223,6 +226,18 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(int64_t n_rows, int64
 // packs the buckets pair after pair -- for sparse buckets (C5: ~0.7 pairs per bucket, where a
 // line per bucket is ~15x the records' bytes).  Descriptors count units of u bytes.
 constexpr int kPairBytes = 12;
+
+// record s of the bucket whose pairs start at base: row8 = 8 * (row in the band), the byte offset of the
+// row's int64 counter in the Gram tile, and the value's bits
+__device__ __forceinline__ void put_record(unsigned char *base, uint32_t s, uint16_t row8, uint32_t bits) {
+    unsigned char *pair = base + (int64_t)kPairBytes * (s >> 1);
+    reinterpret_cast<uint16_t *>(pair)[s & 1] = row8;
+    reinterpret_cast<uint32_t *>(pair + 4)[s & 1] = bits;
+}
+// a bucket of an odd count: the second record of its last pair is (row 0, +0.0) -- adds exactly 0
+__device__ __forceinline__ void pad_odd(unsigned char *base, uint32_t count) {
+    if (count & 1) put_record(base, count, 0, 0u);
+}
 
 __global__ __launch_bounds__(256) void tr_count_kernel(int64_t n_rows, int64_t n_cols, int64_t bw,
                                                        const int64_t *ptr, const int32_t *idx, int32_t *cnt) {
@@ -257,23 +272,17 @@ __global__ __launch_bounds__(256) void tr_fill_kernel(int64_t n_rows, int64_t n_
     const int lane = threadIdx.x & 63;
     const int64_t band = row / bw, band_off = band * n_cols;
     const uint16_t jr = (uint16_t)(row - band * bw);
-    float mx = 0.f;
-    double sm = 0.0;
+    RowStats stats;
     for (int64_t e = ptr[row] + lane; e < ptr[row + 1]; e += 64) {
         const int64_t b = band_off + idx[e];
         const int32_t s = atomicAdd(&cursor[b], 1);
-        unsigned char *pair = t_rec + (int64_t)desc[b].x * unit + (int64_t)kPairBytes * (s >> 1);
-        reinterpret_cast<uint16_t *>(pair)[s & 1] = (uint16_t)(jr * 8u);  // byte offset of the int64 counter
-        reinterpret_cast<float *>(pair + 4)[s & 1] = val[e];
-        mx = fmaxf(mx, fabsf(val[e]));
-        sm += (double)fabsf(val[e]);
+        put_record(t_rec + (int64_t)desc[b].x * unit, (uint32_t)s, (uint16_t)(jr * 8u), __float_as_uint(val[e]));
+        stats.add(val[e]);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    sm = wave_sum<double>(sm);
-    if (lane == 0) { row_max[row] = mx; row_sum[row] = sm; }
+    stats.reduce();
+    if (lane == 0) { row_max[row] = stats.mx; row_sum[row] = stats.sm; }
     // non-negative floats order like their bit patterns
-    if (lane == 0 && mx > 0.f) atomicMax(maxabs_bits, __float_as_uint(mx));
+    if (lane == 0 && stats.mx > 0.f) atomicMax(maxabs_bits, __float_as_uint(stats.mx));
 }
 
 // Gram fixed-point shift of every row r: the largest power of two S = 2^sh with every
@@ -290,17 +299,11 @@ __global__ void tr_rowshift_kernel(int64_t n_rows, const float *row_max, const d
     shift[r] = min(51 - eT, 62 - eB);
 }
 
-// odd buckets: the second record of the last pair is (col 0, +0.0) -- adds exactly 0
 __global__ void tr_pad_fill_kernel(int64_t n, const uint2 *desc, const int32_t *cursor, unsigned char *t_rec,
                                    int32_t unit) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n && (cursor[b] & 1)) {
-        unsigned char *pair = t_rec + (int64_t)desc[b].x * unit + (int64_t)kPairBytes * (cursor[b] >> 1);
-        reinterpret_cast<uint16_t *>(pair)[1] = 0;
-        reinterpret_cast<float *>(pair + 4)[1] = 0.f;
-    }
+    if (b < n) pad_odd(t_rec + (int64_t)desc[b].x * unit, (uint32_t)cursor[b]);
 }
-
 
 // ---------------------------------------------------- staged (binned) transpose fill
 // tr_fill_kernel places every record with a global atomic on its bucket's cursor and two
@@ -314,11 +317,79 @@ __global__ void tr_pad_fill_kernel(int64_t n, const uint2 *desc, const int32_t *
 //      binning workgroups, builds the region's records (a contiguous range of lines: buckets
 //      are ordered by (band, column)) in LDS with LDS cursors -- the odd buckets' padding is
 //      the zero fill -- and writes the image with 16-byte stores.  A region whose image
-//      exceeds the LDS cap falls back to global cursors.
+//      exceeds the LDS cap keeps its cursors in LDS and stores every record straight to t_rec.
+// The placing kernels (this one, the self-counting one and the slot one) share the region
+// descriptor, the walk over a region's sub-runs and the record write below.
 constexpr int kRegionCols = 128;          // columns per region (at least; see tr_region_cols)
 constexpr int kPlaceCap = 48 * 1024;      // LDS image cap of one region
 constexpr int kBinRows = 16;              // rows per binning workgroup (divides every band: band_width % 64 == 0)
 constexpr int kBinCap = 8192;             // entries of one binning workgroup sorted in LDS (64 KiB)
+
+// One region as its placing workgroup sees it: columns [c0, c1) of the band, buckets from b0 on, and the
+// band's binning workgroups [w0, w1), whose sub-runs of the staging buffer hold the region's entries.
+struct TrRegion {
+    int64_t rg, band, g, c0, c1, b0, w0, w1;
+    __device__ int n_buckets() const { return (int)(c1 - c0); }
+};
+__device__ __forceinline__ TrRegion tr_region(int64_t rg, int64_t n_rows, int64_t n_cols, int64_t bw, int32_t cr,
+                                              int32_t nreg) {
+    TrRegion R;
+    R.rg = rg;
+    R.band = rg / nreg;
+    R.g = rg - R.band * nreg;
+    R.c0 = R.g * cr;
+    R.c1 = min<int64_t>(n_cols, R.c0 + cr);
+    R.b0 = R.band * n_cols + R.c0;
+    R.w0 = R.band * bw / kBinRows;
+    R.w1 = cdiv<int64_t>(min<int64_t>(n_rows, (R.band + 1) * bw), kBinRows);
+    return R;
+}
+// The region of this workgroup when dispatch group x = blockIdx % 8 (one XCD) takes a contiguous run of
+// regions: neighbouring regions read neighbouring words of the same table lines, which then come from one L2
+__device__ __forceinline__ int64_t xcd_contiguous_region() {
+    const int64_t nblk = gridDim.x, per8 = nblk / 8, rem8 = nblk % 8;
+    const int64_t x8 = blockIdx.x % 8, k8 = blockIdx.x / 8;
+    return x8 * per8 + (x8 < rem8 ? x8 : rem8) + k8;
+}
+
+// f(x) for every staged entry x of region R, over the 256 threads of the workgroup: a thread takes every
+// 256th binning workgroup of the band and walks its sub-run of the region with kBatch loads in flight.
+template <int kBatch, typename F>
+__device__ __forceinline__ void for_region_entries(const TrRegion &R, int32_t nreg, const int64_t *ptr,
+                                                   const uint2 *staging, const int32_t *tab, F f) {
+    for (int64_t w = R.w0 + threadIdx.x; w < R.w1; w += 256) {
+        const int32_t *trow = tab + w * (nreg + 1);
+        const int32_t o1 = trow[R.g + 1];
+        const uint2 *run = staging + ptr[w * kBinRows];
+        int32_t o = trow[R.g];
+        if constexpr (kBatch > 1) {
+            for (; o + kBatch <= o1; o += kBatch) {
+                uint2 x[kBatch];
+#pragma unroll
+                for (int r = 0; r < kBatch; ++r) x[r] = run[o + r];
+#pragma unroll
+                for (int r = 0; r < kBatch; ++r) f(x[r]);
+            }
+        }
+        for (; o < o1; ++o) f(run[o]);
+    }
+}
+
+// A region's record image in LDS: zeroed before the records land in it (the odd buckets' padding is the
+// zero fill), then stored to its place in t_rec -- whole 16-byte words where the range allows, else the
+// exact byte range (packed records: a multiple of 4 bytes at a 4-byte offset).
+__device__ __forceinline__ void zero_image(unsigned char *image, int64_t img) {
+    for (int64_t i = threadIdx.x; i < (img + 15) / 16; i += 256) reinterpret_cast<uint4 *>(image)[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+__device__ __forceinline__ void store_image(unsigned char *dst, int64_t dst_off, const unsigned char *image, int64_t img) {
+    if (dst_off % 16 == 0 && img % 16 == 0) {
+        uint4 *d = reinterpret_cast<uint4 *>(dst + dst_off);
+        for (int64_t i = threadIdx.x; i < img / 16; i += 256) d[i] = reinterpret_cast<const uint4 *>(image)[i];
+    } else {
+        uint32_t *d = reinterpret_cast<uint32_t *>(dst + dst_off);
+        for (int64_t i = threadIdx.x; i < img / 4; i += 256) d[i] = reinterpret_cast<const uint32_t *>(image)[i];
+    }
+}
 
 __global__ __launch_bounds__(256) void tr_bin_kernel(int64_t n_rows, int64_t n_cols, int64_t bw, int32_t cr,
                                                      int32_t nreg, const int64_t *ptr, const int32_t *idx,
@@ -359,21 +430,14 @@ __global__ __launch_bounds__(256) void tr_bin_kernel(int64_t n_rows, int64_t n_c
     // per-row max / sum of |values| (one wave per row, fixed order: deterministic shifts)
     float wmx = 0.f;
     for (int i = wave; i < nr; i += 4) {
-        float mx = 0.f;
-        double sm = 0.0;
-        for (int32_t e = rp[i] + lane; e < rp[i + 1]; e += 64) {
-            const float a = fabsf(val[E0 + e]);
-            mx = fmaxf(mx, a);
-            sm += (double)a;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        sm = wave_sum<double>(sm);
+        RowStats stats;
+        for (int32_t e = rp[i] + lane; e < rp[i + 1]; e += 64) stats.add(val[E0 + e]);
+        stats.reduce();
         if (lane == 0) {
-            row_max[r0 + i] = mx;
-            row_sum[r0 + i] = sm;
+            row_max[r0 + i] = stats.mx;
+            row_sum[r0 + i] = stats.sm;
         }
-        wmx = fmaxf(wmx, mx);
+        wmx = fmaxf(wmx, stats.mx);
     }
     // the workgroup's max |value| (one store; reduced by tr_maxabs_kernel -- one global atomic per
     // row on a single word serialised the old fill)
@@ -448,8 +512,7 @@ __global__ __launch_bounds__(1024) void tr_maxabs_kernel(int64_t n, const float 
     __shared__ float red[16];
     float m = 0.f;
     for (int64_t i = threadIdx.x; i < n; i += 1024) m = fmaxf(m, wg_max[i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -470,27 +533,22 @@ __global__ __launch_bounds__(256) void phi_row_stats_kernel(int64_t n_rows, cons
     const int64_t r = (int64_t)blockIdx.x * 4 + wave;
     float mx = 0.f;
     if (r < n_rows) {
-        double sm = 0.0;
+        RowStats stats;
         const int64_t e0 = cap > 0 ? r * cap : ptr[r], e1 = cap > 0 ? r * cap + cnt[r] : ptr[r + 1];
         for (int64_t e = e0 + lane; e < e1; e += 256) {  // (up to four loads in flight, summed in e order)
-            float a[4];
+            float v[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) a[q] = e + 64 * q < e1 ? fabsf(val[e + 64 * q]) : 0.f;
+            for (int q = 0; q < 4; ++q) v[q] = e + 64 * q < e1 ? val[e + 64 * q] : 0.f;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (e + 64 * q < e1) {
-                    mx = fmaxf(mx, a[q]);
-                    sm += (double)a[q];
-                }
-            }
+            for (int q = 0; q < 4; ++q)
+                if (e + 64 * q < e1) stats.add(v[q]);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        sm = wave_sum<double>(sm);
+        stats.reduce();
         if (lane == 0) {
-            row_max[r] = mx;
-            row_sum[r] = sm;
+            row_max[r] = stats.mx;
+            row_sum[r] = stats.sm;
         }
+        mx = stats.mx;
     }
     if (lane == 0) red[wave] = mx;
     __syncthreads();
@@ -500,70 +558,40 @@ __global__ __launch_bounds__(256) void phi_row_stats_kernel(int64_t n_rows, cons
 __global__ __launch_bounds__(256) void tr_place_kernel(int64_t n_rows, int64_t n_cols, int64_t bw, int32_t cr,
                                                        int32_t nreg, const int64_t *ptr, const uint2 *desc,
                                                        const int64_t *ent_off, const uint2 *staging,
-                                                       const int32_t *tab, int32_t *gcur, unsigned char *t_rec,
-                                                       int32_t unit) {
+                                                       const int32_t *tab, unsigned char *t_rec, int32_t unit) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tp_smem[];
     const int tid = threadIdx.x;
-    const int64_t band = blockIdx.x / nreg, g = blockIdx.x - band * nreg;
-    const int64_t c0 = g * cr, c1 = min<int64_t>(n_cols, c0 + cr);
-    const int64_t b0 = band * n_cols + c0, b1 = band * n_cols + c1;
-    const int64_t L0 = desc[b0].x, L1 = desc[b1].x;  // (desc[nbk].x = total lines, low word)
+    const TrRegion R = tr_region(blockIdx.x, n_rows, n_cols, bw, cr, nreg);
+    const int64_t b1 = R.b0 + R.n_buckets();
+    const int64_t L0 = desc[R.b0].x, L1 = desc[b1].x;  // (desc[nbk].x = total lines, low word)
     const int64_t img = (L1 - L0) * unit;
-    if (ent_off[b1] == ent_off[b0]) return;
-    // the band's binning workgroups
-    const int64_t w0 = band * bw / kBinRows, w1 = cdiv<int64_t>(min<int64_t>(n_rows, (band + 1) * bw), kBinRows);
+    if (ent_off[b1] == ent_off[R.b0]) return;
     const bool lds = (img + 15) / 16 * 16 <= kPlaceCap;
     uint32_t *lcur = reinterpret_cast<uint32_t *>(tp_smem);   // [cr]
     uint32_t *lline = lcur + cr;                               // [cr] first byte of each bucket in the image
     unsigned char *image = tp_smem + 8 * cr;                   // [img]
-    if (lds) {
-        for (int i = tid; i < c1 - c0; i += 256) {
-            lcur[i] = 0u;
-            lline[i] = (uint32_t)((desc[b0 + i].x - L0) * unit);
-        }
-        for (int64_t i = tid; i < (img + 15) / 16; i += 256) reinterpret_cast<uint4 *>(image)[i] = make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
+    unsigned char *region = t_rec + L0 * unit;
+    for (int i = tid; i < R.n_buckets(); i += 256) {
+        lcur[i] = 0u;
+        lline[i] = (uint32_t)((desc[R.b0 + i].x - L0) * unit);
+        // oversized region: the cursors stay in LDS and the records go straight to t_rec, padding first
+        if (!lds) pad_odd(region + lline[i], (uint32_t)(ent_off[R.b0 + i + 1] - ent_off[R.b0 + i]));
     }
-    for (int64_t w = w0 + tid; w < w1; w += 256) {
-        const int32_t *trow = tab + w * (nreg + 1);
-        const int32_t o0 = trow[g], o1 = trow[g + 1];
-        const uint2 *run = staging + ptr[w * kBinRows];
-        for (int32_t o = o0; o < o1; ++o) {
-            const uint2 x = run[o];
+    if (lds) zero_image(image, img);
+    __syncthreads();
+    auto place = [&](unsigned char *dst) {
+        for_region_entries<1>(R, nreg, ptr, staging, tab, [&](uint2 x) {
             const uint32_t kk = x.x >> 16;
-            if (lds) {
-                const uint32_t s = atomicAdd(&lcur[kk], 1u);
-                unsigned char *pair = image + lline[kk] + kPairBytes * (s >> 1);
-                reinterpret_cast<uint16_t *>(pair)[s & 1] = (uint16_t)(x.x & 0xffffu);
-                reinterpret_cast<uint32_t *>(pair + 4)[s & 1] = x.y;
-            } else {  // oversized region: global cursors (zeroed by the caller)
-                const int64_t b = b0 + kk;
-                const int32_t s = atomicAdd(&gcur[b], 1);
-                unsigned char *pair = t_rec + (int64_t)desc[b].x * unit + (int64_t)kPairBytes * (s >> 1);
-                reinterpret_cast<uint16_t *>(pair)[s & 1] = (uint16_t)(x.x & 0xffffu);
-                reinterpret_cast<uint32_t *>(pair + 4)[s & 1] = x.y;
-            }
-        }
-    }
-    if (lds) {
-        __syncthreads();
-        if ((L0 * unit) % 16 == 0 && img % 16 == 0) {  // whole lines: 16-byte stores
-            uint4 *dst = reinterpret_cast<uint4 *>(t_rec + L0 * unit);
-            for (int64_t i = tid; i < img / 16; i += 256) dst[i] = reinterpret_cast<const uint4 *>(image)[i];
-        } else {  // packed records: the region's exact byte range (a multiple of 4 at a 4-byte offset)
-            uint32_t *dst = reinterpret_cast<uint32_t *>(t_rec + L0 * unit);
-            for (int64_t i = tid; i < img / 4; i += 256) dst[i] = reinterpret_cast<const uint32_t *>(image)[i];
-        }
+            put_record(dst + lline[kk], atomicAdd(&lcur[kk], 1u), (uint16_t)(x.x & 0xffffu), x.y);
+        });
+    };
+    if (!lds) {
+        place(region);
         return;
     }
-    for (int64_t b = b0 + tid; b < b1; b += 256) {  // pad the odd buckets
-        const int32_t c = (int32_t)(ent_off[b + 1] - ent_off[b]);
-        if (c & 1) {
-            unsigned char *pair = t_rec + (int64_t)desc[b].x * unit + (int64_t)kPairBytes * (c >> 1);
-            reinterpret_cast<uint16_t *>(pair)[1] = 0;
-            reinterpret_cast<float *>(pair + 4)[1] = 0.f;
-        }
-    }
+    place(image);
+    __syncthreads();
+    store_image(t_rec, L0 * unit, image, img);
 }
 
 // ---- the plan-free (self-counting) staged transpose: no bucket counts from the walk, no scan over
@@ -579,16 +607,14 @@ __global__ __launch_bounds__(256) void tr_region_units_kernel(int64_t n_rows, in
     const int64_t rg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (rg >= n_regions) return;
     const int lane = threadIdx.x & 63;
-    const int64_t band = rg / nreg, g = rg - band * nreg;
-    const int64_t w0 = band * bw / kBinRows, w1 = cdiv<int64_t>(min<int64_t>(n_rows, (band + 1) * bw), kBinRows);
+    const TrRegion R = tr_region(rg, n_rows, n_cols, bw, cr, nreg);
     int64_t E = 0;
-    for (int64_t w = w0 + lane; w < w1; w += 64) {
+    for (int64_t w = R.w0 + lane; w < R.w1; w += 64) {
         const int32_t *trow = tab + w * (nreg + 1);
-        E += trow[g + 1] - trow[g];
+        E += trow[R.g + 1] - trow[R.g];
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) E += __shfl_xor(E, off, 64);
-    const int64_t nb = min<int64_t>(n_cols, (g + 1) * (int64_t)cr) - g * (int64_t)cr;
+    E = wave_sum<int64_t>(E);
+    const int64_t nb = R.n_buckets();
     if (lane == 0)
         region_units[rg] = E == 0 ? 0 : unit == kPairBytes ? (E + nb + 1) / 2 : (6 * (E + nb)) / unit + nb + 1;
 }
@@ -607,53 +633,34 @@ struct RegionBaseOut {  // region_base[i] = first unit of region i; the total al
 // of the band, in order -- and t_split[b] holds 8 u16 entry offsets, the entries of bucket b before
 // each sub-band.  A symmetric-mode Gram tile on its own (diagonal) band needs only the columns j >= its
 // row, i.e. the sub-bands from its row's on: it starts its bucket streams there.
-// Oversized regions (global cursors) keep arbitrary order and report no split (all offsets 0).
+// Oversized regions (records stored straight to t_rec under one cursor per bucket) keep arbitrary order
+// and report no split (all offsets 0).
 constexpr int kSub = 8;
 
 template <bool kSplit>
 __global__ __launch_bounds__(256) void tr_place_self_kernel(int64_t n_rows, int64_t n_cols, int64_t bw, int32_t cr,
                                                             int32_t nreg, const int64_t *ptr,
                                                             const int64_t *region_base, const uint2 *staging,
-                                                            const int32_t *tab, int32_t *gcur, uint2 *desc,
-                                                            uint4 *t_split, unsigned char *t_rec, int32_t unit) {
+                                                            const int32_t *tab, uint2 *desc, uint4 *t_split,
+                                                            unsigned char *t_rec, int32_t unit) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tps_smem[];
     constexpr int kS = kSplit ? kSub : 1;  // counters per bucket
     const int tid = threadIdx.x;
-    // dispatch group x = blockIdx % 8 (one XCD) takes a contiguous run of regions: neighbouring
-    // regions read neighbouring words of the same table lines, which then come from one L2
-    const int64_t nblk = gridDim.x, per8 = nblk / 8, rem8 = nblk % 8;
-    const int64_t x8 = blockIdx.x % 8, k8 = blockIdx.x / 8;
-    const int64_t rg = x8 * per8 + (x8 < rem8 ? x8 : rem8) + k8, band = rg / nreg, g = rg - band * nreg;
-    const int64_t c0 = g * cr, c1 = min<int64_t>(n_cols, c0 + cr);
-    const int nbk_r = (int)(c1 - c0);
-    const int64_t b0 = band * n_cols + c0;
-    const int64_t U0 = region_base[rg];
+    const TrRegion R = tr_region(xcd_contiguous_region(), n_rows, n_cols, bw, cr, nreg);
+    const int nbk_r = R.n_buckets();
+    const int64_t b0 = R.b0, U0 = region_base[R.rg];
     uint32_t *lcur = reinterpret_cast<uint32_t *>(tps_smem);   // [cr * kS] counts, then cursors
     uint32_t *lline = lcur + cr * kS;                           // [cr] first byte of each bucket in the image
     int32_t *scratch = reinterpret_cast<int32_t *>(lline + cr); // [8]
     unsigned char *image = reinterpret_cast<unsigned char *>(scratch + 8);
-    const int64_t w0 = band * bw / kBinRows, w1 = cdiv<int64_t>(min<int64_t>(n_rows, (band + 1) * bw), kBinRows);
     // (the staged entry's low half is 8 * its row in the band: 8 sub-bands of bw / 8 rows -> x / bw)
     auto slot = [&](uint32_t x) -> uint32_t {
         return kSplit ? (x >> 16) * kSub + (x & 0xffffu) / (uint32_t)bw : (x >> 16);
     };
     for (int i = tid; i < nbk_r * kS; i += 256) lcur[i] = 0u;
     __syncthreads();
-    // pass 1: the region's bucket (and sub-band) counts (four loads in flight per thread)
-    for (int64_t w = w0 + tid; w < w1; w += 256) {
-        const int32_t *trow = tab + w * (nreg + 1);
-        const int32_t o0 = trow[g], o1 = trow[g + 1];
-        const uint2 *run = staging + ptr[w * kBinRows];
-        int32_t o = o0;
-        for (; o + 4 <= o1; o += 4) {
-            uint32_t x[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x[r] = run[o + r].x;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(&lcur[slot(x[r])], 1u);
-        }
-        for (; o < o1; ++o) atomicAdd(&lcur[slot(run[o].x)], 1u);
-    }
+    // pass 1: the region's bucket (and sub-band) counts
+    for_region_entries<4>(R, nreg, ptr, staging, tab, [&](uint2 x) { atomicAdd(&lcur[slot(x.x)], 1u); });
     __syncthreads();
     auto bucket_count = [&](int i) -> uint32_t {
         uint32_t c = 0;
@@ -696,113 +703,34 @@ __global__ __launch_bounds__(256) void tr_place_self_kernel(int64_t n_rows, int6
     __syncthreads();
     const int64_t img = (int64_t)total * unit;
     if (img == 0) return;
-    if (!lds && !kSplit) {
+    unsigned char *region = t_rec + U0 * unit;
+    if (lds) {
+        zero_image(image, img);
+    } else {
         // oversized region (hub columns: 12 % of Enron's regions exceed the LDS image cap, up to ~500 KB):
         // the bucket cursors stay in LDS and every record is stored straight to its place in t_rec --
         // one global atomic per entry in a dependent chain per thread took ~1 ms per launch on Enron
-        for (int i = tid; i < nbk_r; i += 256) {  // the odd buckets' padding record (0, +0.0)
-            const uint32_t c = lcur[i];
-            if (c & 1) {
-                unsigned char *pair = t_rec + (U0 * unit + lline[i]) + (int64_t)kPairBytes * (c >> 1);
-                reinterpret_cast<uint16_t *>(pair)[1] = 0;
-                reinterpret_cast<float *>(pair + 4)[1] = 0.f;
-            }
-        }
+        for (int i = tid; i < nbk_r; i += 256) pad_odd(region + lline[i], bucket_count(i));
         __syncthreads();
-        for (int i = tid; i < nbk_r; i += 256) lcur[i] = 0u;
-        __syncthreads();
-        unsigned char *region = t_rec + U0 * unit;
-        for (int64_t w = w0 + tid; w < w1; w += 256) {
-            const int32_t *trow = tab + w * (nreg + 1);
-            const int32_t o0 = trow[g], o1 = trow[g + 1];
-            const uint2 *run = staging + ptr[w * kBinRows];
-            int32_t o = o0;
-            for (; o + 4 <= o1; o += 4) {  // (four loads in flight per thread)
-                uint2 x[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] = run[o + r];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const uint32_t kk = x[r].x >> 16;
-                    const uint32_t sl = atomicAdd(&lcur[kk], 1u);
-                    unsigned char *pair = region + lline[kk] + kPairBytes * (sl >> 1);
-                    reinterpret_cast<uint16_t *>(pair)[sl & 1] = (uint16_t)(x[r].x & 0xffffu);
-                    reinterpret_cast<uint32_t *>(pair + 4)[sl & 1] = x[r].y;
-                }
-            }
-            for (; o < o1; ++o) {
-                const uint2 x = run[o];
-                const uint32_t kk = x.x >> 16;
-                const uint32_t sl = atomicAdd(&lcur[kk], 1u);
-                unsigned char *pair = region + lline[kk] + kPairBytes * (sl >> 1);
-                reinterpret_cast<uint16_t *>(pair)[sl & 1] = (uint16_t)(x.x & 0xffffu);
-                reinterpret_cast<uint32_t *>(pair + 4)[sl & 1] = x.y;
-            }
-        }
-        return;
     }
-    if (lds) {
-        for (int64_t i = tid; i < (img + 15) / 16; i += 256) reinterpret_cast<uint4 *>(image)[i] = make_uint4(0u, 0u, 0u, 0u);
-    } else {  // oversized region: global cursors of its own buckets, odd buckets padded below
-        for (int i = tid; i < nbk_r; i += 256) {
-            gcur[b0 + i] = 0;
-            const uint32_t c = bucket_count(i);
-            if (c & 1) {
-                unsigned char *pair = t_rec + (U0 * unit + lline[i]) + (int64_t)kPairBytes * (c >> 1);
-                reinterpret_cast<uint16_t *>(pair)[1] = 0;
-                reinterpret_cast<float *>(pair + 4)[1] = 0.f;
-            }
-        }
-    }
-    if (!kSplit) {
+    if (!lds || !kSplit) {  // one cursor per bucket (split, in LDS: the sub-band offsets set above)
         for (int i = tid; i < nbk_r; i += 256) lcur[i] = 0u;
     }
     __syncthreads();
     // pass 2: place the records (the region's entries come from L2: pass 1 just read them)
-    for (int64_t w = w0 + tid; w < w1; w += 256) {
-        const int32_t *trow = tab + w * (nreg + 1);
-        const int32_t o0 = trow[g], o1 = trow[g + 1];
-        const uint2 *run = staging + ptr[w * kBinRows];
-        int32_t o = o0;
-        if (lds) {
-            for (; o + 4 <= o1; o += 4) {  // (four loads in flight per thread)
-                uint2 x[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] = run[o + r];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const uint32_t s = atomicAdd(&lcur[slot(x[r].x)], 1u);
-                    unsigned char *pair = image + lline[x[r].x >> 16] + kPairBytes * (s >> 1);
-                    reinterpret_cast<uint16_t *>(pair)[s & 1] = (uint16_t)(x[r].x & 0xffffu);
-                    reinterpret_cast<uint32_t *>(pair + 4)[s & 1] = x[r].y;
-                }
-            }
-        }
-        for (; o < o1; ++o) {
-            const uint2 x = run[o];
+    auto place = [&](unsigned char *dst, bool by_sub) {
+        for_region_entries<4>(R, nreg, ptr, staging, tab, [&](uint2 x) {
             const uint32_t kk = x.x >> 16;
-            if (lds) {
-                const uint32_t s = atomicAdd(&lcur[slot(x.x)], 1u);
-                unsigned char *pair = image + lline[kk] + kPairBytes * (s >> 1);
-                reinterpret_cast<uint16_t *>(pair)[s & 1] = (uint16_t)(x.x & 0xffffu);
-                reinterpret_cast<uint32_t *>(pair + 4)[s & 1] = x.y;
-            } else {
-                const int32_t s = atomicAdd(&gcur[b0 + kk], 1);
-                unsigned char *pair = t_rec + (U0 * unit + lline[kk]) + (int64_t)kPairBytes * (s >> 1);
-                reinterpret_cast<uint16_t *>(pair)[s & 1] = (uint16_t)(x.x & 0xffffu);
-                reinterpret_cast<uint32_t *>(pair + 4)[s & 1] = x.y;
-            }
-        }
+            put_record(dst + lline[kk], atomicAdd(&lcur[by_sub ? slot(x.x) : kk], 1u), (uint16_t)(x.x & 0xffffu), x.y);
+        });
+    };
+    if (!lds) {
+        place(region, false);
+        return;
     }
-    if (!lds) return;
+    place(image, true);
     __syncthreads();
-    if ((U0 * unit) % 16 == 0 && img % 16 == 0) {
-        uint4 *dst = reinterpret_cast<uint4 *>(t_rec + U0 * unit);
-        for (int64_t i = tid; i < img / 16; i += 256) dst[i] = reinterpret_cast<const uint4 *>(image)[i];
-    } else {
-        uint32_t *dst = reinterpret_cast<uint32_t *>(t_rec + U0 * unit);
-        for (int64_t i = tid; i < img / 4; i += 256) dst[i] = reinterpret_cast<const uint32_t *>(image)[i];
-    }
+    store_image(t_rec, U0 * unit, image, img);
 }
 
 // GRF_REC_SLOT: bucket b owns the 32-byte slot t_rec + 32 b = {u32 pairs, u32 first overflow pair,
@@ -815,31 +743,21 @@ __global__ __launch_bounds__(256) void tr_place_self_kernel(int64_t n_rows, int6
 __global__ __launch_bounds__(256) void tr_place_slots_kernel(int64_t n_rows, int64_t n_cols, int64_t bw, int32_t cr,
                                                              int32_t nreg, int64_t nbk, const int64_t *ptr,
                                                              const int64_t *region_base, const uint2 *staging,
-                                                             const int32_t *tab, int32_t *gcur,
-                                                             unsigned char *t_rec) {
+                                                             const int32_t *tab, unsigned char *t_rec) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tps_smem[];
     const int tid = threadIdx.x;
-    const int64_t nblk = gridDim.x, per8 = nblk / 8, rem8 = nblk % 8;
-    const int64_t x8 = blockIdx.x % 8, k8 = blockIdx.x / 8;
-    const int64_t rg = x8 * per8 + (x8 < rem8 ? x8 : rem8) + k8, band = rg / nreg, g = rg - band * nreg;
-    const int64_t c0 = g * cr, c1 = min<int64_t>(n_cols, c0 + cr);
-    const int nbk_r = (int)(c1 - c0);
-    const int64_t b0 = band * n_cols + c0;
-    const int64_t U0 = region_base[rg];                          // the region's first overflow pair
+    const TrRegion R = tr_region(xcd_contiguous_region(), n_rows, n_cols, bw, cr, nreg);
+    const int nbk_r = R.n_buckets();
+    const int64_t U0 = region_base[R.rg];                        // the region's first overflow pair
     uint32_t *lcur = reinterpret_cast<uint32_t *>(tps_smem);     // [cr] counts, then cursors
     uint32_t *lovf = lcur + cr;                                  // [cr] first overflow pair (local)
     int32_t *scratch = reinterpret_cast<int32_t *>(lovf + cr);   // [8]
     unsigned char *image = reinterpret_cast<unsigned char *>(scratch + 8);
-    unsigned char *slots = t_rec + 32 * b0, *ovf = t_rec + 32 * nbk + (int64_t)kPairBytes * U0;
-    const int64_t w0 = band * bw / kBinRows, w1 = cdiv<int64_t>(min<int64_t>(n_rows, (band + 1) * bw), kBinRows);
+    unsigned char *slots = t_rec + 32 * R.b0, *ovf = t_rec + 32 * nbk + (int64_t)kPairBytes * U0;
     for (int i = tid; i < nbk_r; i += 256) lcur[i] = 0u;
     __syncthreads();
-    for (int64_t w = w0 + tid; w < w1; w += 256) {  // pass 1: the region's bucket counts
-        const int32_t *trow = tab + w * (nreg + 1);
-        const int32_t o0 = trow[g], o1 = trow[g + 1];
-        const uint2 *run = staging + ptr[w * kBinRows];
-        for (int32_t o = o0; o < o1; ++o) atomicAdd(&lcur[run[o].x >> 16], 1u);
-    }
+    // pass 1: the region's bucket counts
+    for_region_entries<1>(R, nreg, ptr, staging, tab, [&](uint2 x) { atomicAdd(&lcur[x.x >> 16], 1u); });
     __syncthreads();
     const int per = (nbk_r + 255) / 256;
     int32_t sum = 0;
@@ -864,39 +782,24 @@ __global__ __launch_bounds__(256) void tr_place_slots_kernel(int64_t n_rows, int
     }
     const int64_t img = (int64_t)total * kPairBytes;
     if (lds) {
-        for (int64_t i = tid; i < (img + 15) / 16; i += 256) reinterpret_cast<uint4 *>(image)[i] = make_uint4(0u, 0u, 0u, 0u);
+        zero_image(image, img);
     } else {  // oversized region: overflow pairs straight to global, zeroed first
         for (int64_t i = tid; i < img / 4; i += 256) reinterpret_cast<uint32_t *>(ovf)[i] = 0u;
     }
     __threadfence_block();
     __syncthreads();
-    for (int64_t w = w0 + tid; w < w1; w += 256) {  // pass 2: place the entries
-        const int32_t *trow = tab + w * (nreg + 1);
-        const int32_t o0 = trow[g], o1 = trow[g + 1];
-        const uint2 *run = staging + ptr[w * kBinRows];
-        for (int32_t o = o0; o < o1; ++o) {
-            const uint2 x = run[o];
-            const uint32_t kk = x.x >> 16;
-            const uint32_t s = atomicAdd(&lcur[kk], 1u);
-            unsigned char *pair;
-            uint32_t half;
-            if (s < 4) {
-                pair = slots + 32 * (int64_t)kk + 8 + kPairBytes * (s >> 1);
-                half = s & 1;
-            } else {
-                const uint32_t q = s - 4;
-                pair = (lds ? image : ovf) + kPairBytes * (int64_t)(lovf[kk] + (q >> 1));
-                half = q & 1;
-            }
-            reinterpret_cast<uint16_t *>(pair)[half] = (uint16_t)(x.x & 0xffffu);
-            reinterpret_cast<uint32_t *>(pair + 4)[half] = x.y;
-        }
-    }
+    // pass 2: the first four entries of a bucket into its slot (after the 8-byte header), the rest into its overflow pairs
+    unsigned char *pairs = lds ? image : ovf;
+    for_region_entries<1>(R, nreg, ptr, staging, tab, [&](uint2 x) {
+        const uint32_t kk = x.x >> 16;
+        const uint32_t s = atomicAdd(&lcur[kk], 1u);
+        unsigned char *base = s < 4 ? slots + 32 * (int64_t)kk + 8 : pairs + kPairBytes * (int64_t)lovf[kk];
+        put_record(base, s < 4 ? s : s - 4, (uint16_t)(x.x & 0xffffu), x.y);
+    });
     if (!lds || img == 0) return;
     __syncthreads();
     uint32_t *dst = reinterpret_cast<uint32_t *>(ovf);
     for (int64_t i = tid; i < img / 4; i += 256) dst[i] = reinterpret_cast<const uint32_t *>(image)[i];
-    (void)gcur;
 }
 
 // Region width: at most 4096 regions per band, and every placing workgroup reads one table
@@ -969,27 +872,101 @@ int32_t grf_compact_rows(int64_t n_rows, int64_t cap, const int32_t *cnt, const 
 
 static size_t tr_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
-size_t grf_transpose_workspace_bytes(int64_t n_buckets) {
-    return 2 * tr_align((size_t)n_buckets * sizeof(int32_t)) + tr_align((size_t)(n_buckets + 1) * sizeof(int64_t)) +
-           scan_ws_bytes(n_buckets);
+// Byte offsets of the plan's and the planned fills' workspace: [cnt: bucket counts, the atomic fill's cursors |
+// row_max (n_rows <= nbk) | ent_off (nbk + 1 entries before each bucket; the atomic fill's row_sum) | scan scratch]
+struct TrPlanWs {
+    size_t row_max, ent_off, scan, bytes;
+    explicit TrPlanWs(int64_t nbk)
+        : row_max(tr_align((size_t)nbk * sizeof(int32_t))), ent_off(2 * row_max),
+          scan(ent_off + tr_align((size_t)(nbk + 1) * sizeof(int64_t))), bytes(scan + scan_ws_bytes(nbk)) {}
+};
+
+// The staging buffer of the staged fills: [ent: the nnz staged entries | row_sum | tab: nreg + 1 region offsets
+// per binning workgroup | wg_max: a max per binning workgroup], with the region width it is laid out for
+struct TrStaging {
+    int32_t cr;
+    int64_t nreg, nwg;
+    size_t row_sum, tab, wg_max, bytes;
+    TrStaging(int64_t n_rows, int64_t n_cols, int64_t nnz)
+        : cr(tr_region_cols(n_rows, n_cols)), nreg(cdiv<int64_t>(n_cols, cr)), nwg(cdiv<int64_t>(n_rows, kBinRows)),
+          row_sum(tr_align((size_t)nnz * 8)), tab(row_sum + tr_align((size_t)std::max<int64_t>(n_rows, 1) * 8)),
+          wg_max(tab + tr_align((size_t)std::max<int64_t>(nwg, 1) * (nreg + 1) * 4)),
+          bytes(wg_max + tr_align((size_t)std::max<int64_t>(nwg, 1) * 4)) {}
+};
+
+// The self-counting transpose's workspace: [row_max | region_units (n_regions + 1) | region_base (n_regions + 1) |
+// 4 bytes per bucket, unused (the global cursors of oversized regions before their cursors moved to LDS; the size
+// function is part of the ABI) | scan scratch]
+struct TrSelfWs {
+    int64_t n_regions;
+    size_t region_units, region_base, scan, bytes;
+    TrSelfWs(int64_t n_rows, int64_t n_cols, int64_t band_width) {
+        const int64_t nb = cdiv<int64_t>(std::max<int64_t>(n_rows, 1), band_width);
+        n_regions = nb * cdiv<int64_t>(n_cols, tr_region_cols(n_rows, n_cols));
+        region_units = tr_align((size_t)std::max<int64_t>(n_rows, 1) * 4);
+        region_base = region_units + tr_align((size_t)(n_regions + 1) * 8);
+        scan = region_base + tr_align((size_t)(n_regions + 1) * 8) + tr_align((size_t)nb * n_cols * 4);
+        bytes = scan + scan_ws_bytes(n_regions);
+    }
+};
+
+// The argument checks the transpose entries share, in the order every entry reports them: `args` is the entry's own
+// pointer and size conditions; the plan has no t_rec (NULL), only the staged fills bin (band_width, region width) and
+// only the self-counting one knows GRF_REC_SLOT and the split.
+static int32_t tr_check(const char *who, bool args, int64_t n_rows, int64_t n_cols, int64_t band_width,
+                        int32_t rec_unit, const void *t_rec, bool staged, bool slot_ok = false, bool split = false) {
+    GRF_REQUIRE(n_rows >= 0 && n_cols > 0 && band_width > 0 && band_width <= 8192 && args, GRF_EINVAL,
+                "%s: bad arguments", who);
+    GRF_REQUIRE(rec_unit == GRF_REC_LINE || rec_unit == GRF_REC_PACKED || (slot_ok && rec_unit == GRF_REC_SLOT),
+                GRF_EINVAL, "%s: rec_unit must be GRF_REC_LINE%s", who,
+                slot_ok ? ", GRF_REC_PACKED or GRF_REC_SLOT" : " or GRF_REC_PACKED");
+    GRF_REQUIRE(rec_unit != GRF_REC_SLOT || !split, GRF_EUNSUPPORTED, "%s: GRF_REC_SLOT has no sub-band split", who);
+    GRF_REQUIRE(!staged || band_width % 64 == 0, GRF_EUNSUPPORTED, "%s: band_width must be a multiple of 64", who);
+    GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL, "%s: t_rec must be 128-byte aligned", who);
+    GRF_REQUIRE(!staged || tr_region_cols(n_rows, n_cols) <= 65536, GRF_EUNSUPPORTED, "%s: too many columns", who);
+    return GRF_OK;
 }
+
+// max |Phi| from the workgroup maxima, then every row's Gram shift
+static int32_t row_shifts_finish(hipStream_t st, int64_t n_rows, int64_t nwg, const float *wg_max, const float *row_max,
+                                 const double *row_sum, float *maxabs, int32_t *shift) {
+    tr_maxabs_kernel<<<1, 1024, 0, st>>>(nwg, wg_max, maxabs);
+    GRF_CHECK_LAUNCH("tr_maxabs_kernel");
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 256), 256, "tr_rowshift_kernel");
+    tr_rowshift_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 256), 256, 0, st>>>(n_rows, row_max, row_sum, maxabs, shift);
+    GRF_CHECK_LAUNCH("tr_rowshift_kernel");
+    return GRF_OK;
+}
+
+// tr_bin_kernel over the whole Phi into the staging buffer, then the shifts from its row statistics
+static int32_t tr_bin_and_shifts(hipStream_t st, int64_t n_rows, int64_t n_cols, int64_t band_width, const TrStaging &sg,
+                                 const int64_t *ptr, const int32_t *idx, const float *val, void *staging, float *row_max,
+                                 float *t_maxabs, int32_t *t_rowshift) {
+    char *s = (char *)staging;
+    const size_t lds = (size_t)kBinCap * 8 + (size_t)sg.nreg * 4 + (kBinRows + 1 + 8) * 4;
+    GRF_REQUIRE_GRID(sg.nwg, 256, "tr_bin_kernel");
+    tr_bin_kernel<<<(unsigned)sg.nwg, 256, lds, st>>>(n_rows, n_cols, band_width, sg.cr, (int32_t)sg.nreg, ptr, idx, val,
+                                                     (uint2 *)s, (int32_t *)(s + sg.tab), (float *)(s + sg.wg_max),
+                                                     row_max, (double *)(s + sg.row_sum));
+    GRF_CHECK_LAUNCH("tr_bin_kernel");
+    return row_shifts_finish(st, n_rows, sg.nwg, (const float *)(s + sg.wg_max), row_max,
+                             (const double *)(s + sg.row_sum), t_maxabs, t_rowshift);
+}
+
+size_t grf_transpose_workspace_bytes(int64_t n_buckets) { return TrPlanWs(n_buckets).bytes; }
 
 int32_t grf_transpose_banded_plan(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
                                   const int64_t *ptr, const int32_t *idx, uint32_t *t_desc, int32_t counted,
                                   void *workspace, size_t workspace_bytes, grf_stream_t stream) {
-    GRF_REQUIRE(n_rows >= 0 && n_cols > 0 && band_width > 0 && band_width <= 8192 && ptr && idx && t_desc,
-                GRF_EINVAL, "grf_transpose_banded_plan: bad arguments");
-    GRF_REQUIRE(rec_unit == GRF_REC_LINE || rec_unit == GRF_REC_PACKED, GRF_EINVAL,
-                "grf_transpose_banded_plan: rec_unit must be GRF_REC_LINE or GRF_REC_PACKED");
+    int32_t rc = tr_check("grf_transpose_banded_plan", ptr && idx && t_desc, n_rows, n_cols, band_width, rec_unit,
+                          nullptr, false);
+    if (rc != GRF_OK) return rc;
     const int64_t nb = cdiv<int64_t>(n_rows, band_width), nbk = nb * n_cols;
-    GRF_REQUIRE(workspace_bytes >= grf_transpose_workspace_bytes(nbk), GRF_EINVAL,
-                "grf_transpose_banded_plan: workspace too small (%zu < %zu)", workspace_bytes,
-                grf_transpose_workspace_bytes(nbk));
+    const TrPlanWs ws(nbk);
+    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_plan: workspace too small (%zu < %zu)",
+                workspace_bytes, ws.bytes);
     hipStream_t st = S(stream);
-    char *w = (char *)workspace;
-    int32_t *cnt = (int32_t *)w;
-    // (the workspace layout is shared with the fills: [cnt | row_max | ent_off | scan scratch])
-    void *scan_ws = w + 2 * tr_align((size_t)nbk * 4) + tr_align((size_t)(nbk + 1) * 8);
+    int32_t *cnt = (int32_t *)workspace;
     if (!counted) GRF_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)nbk * sizeof(int32_t), st));
     if (n_rows > 0 && !counted) {
         GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "tr_count_kernel");
@@ -999,27 +976,25 @@ int32_t grf_transpose_banded_plan(int64_t n_rows, int64_t n_cols, int64_t band_w
     }
     // units per bucket -> exclusive scan -> descriptors, in one scan (no units / offsets arrays)
     return scan_exclusive<int32_t>(nbk, cnt, TrUnitsMap{rec_unit}, TrDescOut{cnt, reinterpret_cast<uint2 *>(t_desc)},
-                                   (int64_t *)scan_ws, st);
+                                   (int64_t *)((char *)workspace + ws.scan), st);
 }
 
 int32_t grf_transpose_banded_fill(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
                                   const int64_t *ptr, const int32_t *idx, const float *val, const uint32_t *t_desc,
                                   void *t_rec, int64_t t_rec_bytes, float *t_maxabs, int32_t *t_rowshift,
                                   void *workspace, size_t workspace_bytes, grf_stream_t stream) {
-    GRF_REQUIRE(n_rows >= 0 && n_cols > 0 && band_width > 0 && band_width <= 8192 && ptr && idx && val && t_desc &&
-                    t_rec && t_maxabs && t_rowshift && t_rec_bytes >= 0,
-                GRF_EINVAL, "grf_transpose_banded_fill: bad arguments");
-    GRF_REQUIRE(rec_unit == GRF_REC_LINE || rec_unit == GRF_REC_PACKED, GRF_EINVAL,
-                "grf_transpose_banded_fill: rec_unit must be GRF_REC_LINE or GRF_REC_PACKED");
-    GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL, "grf_transpose_banded_fill: t_rec must be 128-byte aligned");
+    int32_t rc = tr_check("grf_transpose_banded_fill",
+                          ptr && idx && val && t_desc && t_rec && t_maxabs && t_rowshift && t_rec_bytes >= 0, n_rows,
+                          n_cols, band_width, rec_unit, t_rec, false);
+    if (rc != GRF_OK) return rc;
     const int64_t nb = cdiv<int64_t>(n_rows, band_width), nbk = nb * n_cols;
-    GRF_REQUIRE(workspace_bytes >= grf_transpose_workspace_bytes(nbk), GRF_EINVAL,
-                "grf_transpose_banded_fill: workspace too small");
+    const TrPlanWs ws(nbk);
+    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_fill: workspace too small");
     hipStream_t st = S(stream);
     char *w = (char *)workspace;
     int32_t *cursor = (int32_t *)w;
-    float *row_max = (float *)(w + tr_align((size_t)nbk * 4));                                // n_rows <= nbk
-    double *row_sum = (double *)(w + 2 * tr_align((size_t)nbk * 4));                         // n_rows <= nbk + 1
+    float *row_max = (float *)(w + ws.row_max);
+    double *row_sum = (double *)(w + ws.ent_off);  // (n_rows <= nbk + 1)
     const uint2 *desc = reinterpret_cast<const uint2 *>(t_desc);
     GRF_CHECK_HIP(hipMemsetAsync(cursor, 0, (size_t)nbk * sizeof(int32_t), st));
     GRF_CHECK_HIP(hipMemsetAsync(t_maxabs, 0, sizeof(float), st));
@@ -1041,12 +1016,9 @@ int32_t grf_transpose_banded_fill(int64_t n_rows, int64_t n_cols, int64_t band_w
     return GRF_OK;
 }
 
-
 size_t grf_transpose_staging_bytes(int64_t n_rows, int64_t n_cols, int64_t band_width, int64_t nnz) {
     if (n_cols <= 0 || band_width <= 0) return 0;
-    const int64_t nreg = cdiv<int64_t>(n_cols, tr_region_cols(n_rows, n_cols)), nwg = cdiv<int64_t>(n_rows, kBinRows);
-    return tr_align((size_t)nnz * 8) + tr_align((size_t)std::max<int64_t>(n_rows, 1) * 8) +
-           tr_align((size_t)std::max<int64_t>(nwg, 1) * (nreg + 1) * 4) + tr_align((size_t)std::max<int64_t>(nwg, 1) * 4);
+    return TrStaging(n_rows, n_cols, nnz).bytes;
 }
 
 int32_t grf_transpose_banded_fill_staged(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
@@ -1054,76 +1026,47 @@ int32_t grf_transpose_banded_fill_staged(int64_t n_rows, int64_t n_cols, int64_t
                                          const uint32_t *t_desc, void *t_rec, int64_t t_rec_bytes, float *t_maxabs,
                                          int32_t *t_rowshift, void *workspace, size_t workspace_bytes, int64_t nnz,
                                          void *staging, size_t staging_bytes, grf_stream_t stream) {
-    GRF_REQUIRE(n_rows >= 0 && n_cols > 0 && band_width > 0 && band_width <= 8192 && ptr && idx && val && t_desc &&
-                    t_rec && t_maxabs && t_rowshift && t_rec_bytes >= 0 && staging,
-                GRF_EINVAL, "grf_transpose_banded_fill_staged: bad arguments");
-    GRF_REQUIRE(rec_unit == GRF_REC_LINE || rec_unit == GRF_REC_PACKED, GRF_EINVAL,
-                "grf_transpose_banded_fill_staged: rec_unit must be GRF_REC_LINE or GRF_REC_PACKED");
-    GRF_REQUIRE(band_width % 64 == 0, GRF_EUNSUPPORTED,
-                "grf_transpose_banded_fill_staged: band_width must be a multiple of 64");
-    GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL,
-                "grf_transpose_banded_fill_staged: t_rec must be 128-byte aligned");
+    int32_t rc = tr_check("grf_transpose_banded_fill_staged",
+                          ptr && idx && val && t_desc && t_rec && t_maxabs && t_rowshift && t_rec_bytes >= 0 && staging,
+                          n_rows, n_cols, band_width, rec_unit, t_rec, true);
+    if (rc != GRF_OK) return rc;
     const int64_t nb = cdiv<int64_t>(n_rows, band_width), nbk = nb * n_cols;
-    const int32_t cr = tr_region_cols(n_rows, n_cols);
-    GRF_REQUIRE(cr <= 65536, GRF_EUNSUPPORTED, "grf_transpose_banded_fill_staged: too many columns");
-    const int32_t nreg = (int32_t)cdiv<int64_t>(n_cols, cr);
-    GRF_REQUIRE(workspace_bytes >= grf_transpose_workspace_bytes(nbk), GRF_EINVAL,
-                "grf_transpose_banded_fill_staged: workspace too small");
-    GRF_REQUIRE(nnz >= 0 && staging_bytes >= grf_transpose_staging_bytes(n_rows, n_cols, band_width, nnz), GRF_EINVAL,
-                "grf_transpose_banded_fill_staged: staging too small (%zu < %zu)", staging_bytes,
-                grf_transpose_staging_bytes(n_rows, n_cols, band_width, nnz));
+    const TrPlanWs ws(nbk);
+    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_fill_staged: workspace too small");
+    const TrStaging sg(n_rows, n_cols, nnz);
+    GRF_REQUIRE(nnz >= 0 && staging_bytes >= sg.bytes, GRF_EINVAL,
+                "grf_transpose_banded_fill_staged: staging too small (%zu < %zu)", staging_bytes, sg.bytes);
     hipStream_t st = S(stream);
-    // workspace: [cnt: bucket counts from the plan | row_max | ent_off (nbk + 1) | scan scratch]
     char *w = (char *)workspace;
-    int32_t *cnt = (int32_t *)w;
-    float *row_max = (float *)(w + tr_align((size_t)nbk * 4));
-    int64_t *ent_off = (int64_t *)(w + 2 * tr_align((size_t)nbk * 4));
-    void *scan_ws = w + 2 * tr_align((size_t)nbk * 4) + tr_align((size_t)(nbk + 1) * 8);
-    char *sg = (char *)staging;
-    uint2 *ent = (uint2 *)sg;
-    double *row_sum = (double *)(sg + tr_align((size_t)nnz * 8));
-    int32_t *tab = (int32_t *)(sg + tr_align((size_t)nnz * 8) + tr_align((size_t)std::max<int64_t>(n_rows, 1) * 8));
-    const int64_t nwg = cdiv<int64_t>(n_rows, kBinRows);
-    float *wg_max = (float *)((char *)tab + tr_align((size_t)std::max<int64_t>(nwg, 1) * (nreg + 1) * 4));
-    const uint2 *desc = reinterpret_cast<const uint2 *>(t_desc);
-    int32_t rc = scan_counts_i32(nbk, cnt, ent_off, scan_ws, scan_ws_bytes(nbk), st);  // entries before each bucket
+    int32_t *cnt = (int32_t *)w;  // (the bucket counts from the plan)
+    int64_t *ent_off = (int64_t *)(w + ws.ent_off);
+    rc = scan_counts_i32(nbk, cnt, ent_off, w + ws.scan, scan_ws_bytes(nbk), st);  // entries before each bucket
     if (rc != GRF_OK) return rc;
     GRF_CHECK_HIP(hipMemsetAsync(t_maxabs, 0, sizeof(float), st));
     if (n_rows == 0) return GRF_OK;
-    const size_t lds1 = (size_t)kBinCap * 8 + (size_t)nreg * 4 + (kBinRows + 1 + 8) * 4;
-    GRF_REQUIRE_GRID(nwg, 256, "tr_bin_kernel");
-    tr_bin_kernel<<<(unsigned)nwg, 256, lds1, st>>>(n_rows, n_cols, band_width, cr, nreg, ptr, idx, val, ent, tab,
-                                                    wg_max, row_max, row_sum);
-    GRF_CHECK_LAUNCH("tr_bin_kernel");
-    tr_maxabs_kernel<<<1, 1024, 0, st>>>(nwg, wg_max, t_maxabs);
-    GRF_CHECK_LAUNCH("tr_maxabs_kernel");
-    GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 256), 256, "tr_rowshift_kernel");
-    tr_rowshift_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 256), 256, 0, st>>>(n_rows, row_max, row_sum, t_maxabs,
-                                                                            t_rowshift);
-    GRF_CHECK_LAUNCH("tr_rowshift_kernel");
-    GRF_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)nbk * sizeof(int32_t), st));  // fallback cursors
-    const int64_t n_regions = nb * nreg;
-    const size_t lds2 = (size_t)8 * cr + kPlaceCap;
+    rc = tr_bin_and_shifts(st, n_rows, n_cols, band_width, sg, ptr, idx, val, staging, (float *)(w + ws.row_max), t_maxabs,
+                           t_rowshift);
+    if (rc != GRF_OK) return rc;
+    const int64_t n_regions = nb * sg.nreg;
+    const size_t lds2 = (size_t)8 * sg.cr + kPlaceCap;
     GRF_REQUIRE_GRID(n_regions, 256, "tr_place_kernel");
-    tr_place_kernel<<<(unsigned)n_regions, 256, lds2, st>>>(n_rows, n_cols, band_width, cr, nreg, ptr, desc, ent_off,
-                                                            ent, tab, cnt, (unsigned char *)t_rec, rec_unit);
+    tr_place_kernel<<<(unsigned)n_regions, 256, lds2, st>>>(
+        n_rows, n_cols, band_width, sg.cr, (int32_t)sg.nreg, ptr, reinterpret_cast<const uint2 *>(t_desc), ent_off,
+        (const uint2 *)staging, (const int32_t *)((char *)staging + sg.tab), (unsigned char *)t_rec, rec_unit);
     GRF_CHECK_LAUNCH("tr_place_kernel");
     return GRF_OK;
 }
 
 size_t grf_transpose_self_workspace_bytes(int64_t n_rows, int64_t n_cols, int64_t band_width) {
     if (n_cols <= 0 || band_width <= 0) return 16;
-    const int64_t nb = cdiv<int64_t>(std::max<int64_t>(n_rows, 1), band_width);
-    const int64_t n_regions = nb * cdiv<int64_t>(n_cols, tr_region_cols(n_rows, n_cols));
-    return tr_align((size_t)std::max<int64_t>(n_rows, 1) * 4) + 2 * tr_align((size_t)(n_regions + 1) * 8) +
-           tr_align((size_t)nb * n_cols * 4) + scan_ws_bytes(n_regions);
+    return TrSelfWs(n_rows, n_cols, band_width).bytes;
 }
 
 int64_t grf_transpose_self_units_bound(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
                                        int64_t nnz) {
     if (n_cols <= 0 || band_width <= 0) return 1;
     const int64_t nb = cdiv<int64_t>(std::max<int64_t>(n_rows, 1), band_width), nbk = nb * n_cols;
-    const int64_t n_regions = nb * cdiv<int64_t>(n_cols, tr_region_cols(n_rows, n_cols));
+    const int64_t n_regions = TrSelfWs(n_rows, n_cols, band_width).n_regions;
     // the sum of tr_region_units over the regions, for any split of nnz entries
     if (rec_unit == GRF_REC_PACKED) return (nnz + nbk) / 2 + n_regions + 1;
     // GRF_REC_SLOT: 32-byte units covering the slots and the overflow pairs (at most the packed bound)
@@ -1136,91 +1079,61 @@ int32_t grf_transpose_banded_self(int64_t n_rows, int64_t n_cols, int64_t band_w
                                   void *t_split, void *t_rec, int64_t t_rec_bytes, float *t_maxabs, int32_t *t_rowshift,
                                   void *workspace, size_t workspace_bytes, int64_t nnz, void *staging,
                                   size_t staging_bytes, grf_stream_t stream) {
-    GRF_REQUIRE(n_rows >= 0 && n_cols > 0 && band_width > 0 && band_width <= 8192 && ptr && idx && val && t_desc &&
-                    t_rec && t_maxabs && t_rowshift && t_rec_bytes >= 0 && staging && workspace,
-                GRF_EINVAL, "grf_transpose_banded_self: bad arguments");
-    GRF_REQUIRE(rec_unit == GRF_REC_LINE || rec_unit == GRF_REC_PACKED || rec_unit == GRF_REC_SLOT, GRF_EINVAL,
-                "grf_transpose_banded_self: rec_unit must be GRF_REC_LINE, GRF_REC_PACKED or GRF_REC_SLOT");
-    GRF_REQUIRE(rec_unit != GRF_REC_SLOT || !t_split, GRF_EUNSUPPORTED,
-                "grf_transpose_banded_self: GRF_REC_SLOT has no sub-band split");
-    GRF_REQUIRE(band_width % 64 == 0, GRF_EUNSUPPORTED, "grf_transpose_banded_self: band_width must be a multiple of 64");
-    GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL, "grf_transpose_banded_self: t_rec must be 128-byte aligned");
+    int32_t rc = tr_check("grf_transpose_banded_self",
+                          ptr && idx && val && t_desc && t_rec && t_maxabs && t_rowshift && t_rec_bytes >= 0 && staging &&
+                              workspace,
+                          n_rows, n_cols, band_width, rec_unit, t_rec, true, true, t_split != nullptr);
+    if (rc != GRF_OK) return rc;
     const int64_t nb = cdiv<int64_t>(n_rows, band_width), nbk = nb * n_cols;
-    const int32_t cr = tr_region_cols(n_rows, n_cols);
-    GRF_REQUIRE(cr <= 65536, GRF_EUNSUPPORTED, "grf_transpose_banded_self: too many columns");
-    const int32_t nreg = (int32_t)cdiv<int64_t>(n_cols, cr);
-    GRF_REQUIRE(workspace_bytes >= grf_transpose_self_workspace_bytes(n_rows, n_cols, band_width), GRF_EINVAL,
-                "grf_transpose_banded_self: workspace too small");
-    GRF_REQUIRE(nnz >= 0 && staging_bytes >= grf_transpose_staging_bytes(n_rows, n_cols, band_width, nnz), GRF_EINVAL,
-                "grf_transpose_banded_self: staging too small");
+    const TrSelfWs ws(n_rows, n_cols, band_width);
+    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_self: workspace too small");
+    const TrStaging sg(n_rows, n_cols, nnz);
+    GRF_REQUIRE(nnz >= 0 && staging_bytes >= sg.bytes, GRF_EINVAL, "grf_transpose_banded_self: staging too small");
     GRF_REQUIRE(t_rec_bytes >= grf_transpose_self_units_bound(n_rows, n_cols, band_width, rec_unit, nnz) * rec_unit,
                 GRF_ECAPACITY, "grf_transpose_banded_self: t_rec too small for the region slabs");
     hipStream_t st = S(stream);
-    const int64_t n_regions = nb * nreg;
-    char *w = (char *)workspace;
-    float *row_max = (float *)w;
-    w += tr_align((size_t)std::max<int64_t>(n_rows, 1) * 4);
-    int64_t *region_units = (int64_t *)w;
-    w += tr_align((size_t)(n_regions + 1) * 8);
-    int64_t *region_base = (int64_t *)w;
-    w += tr_align((size_t)(n_regions + 1) * 8);
-    int32_t *gcur = (int32_t *)w;  // (fallback cursors of oversized regions; zeroed by their owners)
-    w += tr_align((size_t)nbk * 4);
-    void *scan_ws = w;
-    char *sg = (char *)staging;
-    uint2 *ent = (uint2 *)sg;
-    double *row_sum = (double *)(sg + tr_align((size_t)nnz * 8));
-    int32_t *tab = (int32_t *)(sg + tr_align((size_t)nnz * 8) + tr_align((size_t)std::max<int64_t>(n_rows, 1) * 8));
-    const int64_t nwg = cdiv<int64_t>(n_rows, kBinRows);
-    float *wg_max = (float *)((char *)tab + tr_align((size_t)std::max<int64_t>(nwg, 1) * (nreg + 1) * 4));
     uint2 *desc = reinterpret_cast<uint2 *>(t_desc);
     GRF_CHECK_HIP(hipMemsetAsync(t_maxabs, 0, sizeof(float), st));
     if (n_rows == 0) {
         GRF_CHECK_HIP(hipMemsetAsync(t_desc, 0, (size_t)(nbk + 1) * 8, st));
         return GRF_OK;
     }
-    GRF_REQUIRE(!t_split || band_width <= 8192, GRF_EUNSUPPORTED,
-                "grf_transpose_banded_self: the sub-band split needs band_width <= 8192 (u16 offsets)");
     GRF_REQUIRE(((uintptr_t)t_split & 15) == 0, GRF_EINVAL, "grf_transpose_banded_self: t_split must be 16-byte aligned");
-    const size_t lds1 = (size_t)kBinCap * 8 + (size_t)nreg * 4 + (kBinRows + 1 + 8) * 4;
-    GRF_REQUIRE_GRID(nwg, 256, "tr_bin_kernel");
-    tr_bin_kernel<<<(unsigned)nwg, 256, lds1, st>>>(n_rows, n_cols, band_width, cr, nreg, ptr, idx, val, ent, tab,
-                                                    wg_max, row_max, row_sum);
-    GRF_CHECK_LAUNCH("tr_bin_kernel");
-    tr_maxabs_kernel<<<1, 1024, 0, st>>>(nwg, wg_max, t_maxabs);
-    GRF_CHECK_LAUNCH("tr_maxabs_kernel");
-    GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 256), 256, "tr_rowshift_kernel");
-    tr_rowshift_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 256), 256, 0, st>>>(n_rows, row_max, row_sum, t_maxabs,
-                                                                            t_rowshift);
-    GRF_CHECK_LAUNCH("tr_rowshift_kernel");
+    char *w = (char *)workspace;
+    int64_t *region_units = (int64_t *)(w + ws.region_units), *region_base = (int64_t *)(w + ws.region_base);
+    const uint2 *ent = (const uint2 *)staging;
+    const int32_t *tab = (const int32_t *)((char *)staging + sg.tab);
+    const int32_t cr = sg.cr, nreg = (int32_t)sg.nreg;
+    const int64_t n_regions = ws.n_regions;  // (n_rows > 0: nb * nreg)
+    rc = tr_bin_and_shifts(st, n_rows, n_cols, band_width, sg, ptr, idx, val, staging, (float *)w, t_maxabs, t_rowshift);
+    if (rc != GRF_OK) return rc;
     GRF_REQUIRE_GRID(cdiv<int64_t>(n_regions, 4), 256, "tr_region_units_kernel");
     tr_region_units_kernel<<<(unsigned)cdiv<int64_t>(n_regions, 4), 256, 0, st>>>(n_rows, n_cols, band_width, cr, nreg,
                                                                                  n_regions, tab,
                                                                                  rec_unit == GRF_REC_SLOT ? kPairBytes : rec_unit,
                                                                                  region_units);
     GRF_CHECK_LAUNCH("tr_region_units_kernel");
-    int32_t rc = scan_exclusive<int64_t>(n_regions, region_units, ScanIdentity{},
-                                         RegionBaseOut{region_base, desc + nbk}, (int64_t *)scan_ws, st);
+    rc = scan_exclusive<int64_t>(n_regions, region_units, ScanIdentity{}, RegionBaseOut{region_base, desc + nbk},
+                                 (int64_t *)(w + ws.scan), st);
     if (rc != GRF_OK) return rc;
     GRF_REQUIRE_GRID(n_regions, 256, "tr_place_self_kernel");
     if (rec_unit == GRF_REC_SLOT) {
         const size_t lds2 = (size_t)8 * cr + 32 + kPlaceCap;
         tr_place_slots_kernel<<<(unsigned)n_regions, 256, lds2, st>>>(n_rows, n_cols, band_width, cr, nreg, nbk, ptr,
-                                                                       region_base, ent, tab, gcur,
-                                                                       (unsigned char *)t_rec);
+                                                                       region_base, ent, tab, (unsigned char *)t_rec);
         GRF_CHECK_LAUNCH("tr_place_slots_kernel");
         return GRF_OK;
     }
     if (t_split) {
         const size_t lds2 = (size_t)4 * cr * (kSub + 1) + 32 + kPlaceCap;
         tr_place_self_kernel<true><<<(unsigned)n_regions, 256, lds2, st>>>(
-            n_rows, n_cols, band_width, cr, nreg, ptr, region_base, ent, tab, gcur, desc, (uint4 *)t_split,
+            n_rows, n_cols, band_width, cr, nreg, ptr, region_base, ent, tab, desc, (uint4 *)t_split,
             (unsigned char *)t_rec, rec_unit);
     } else {
         const size_t lds2 = (size_t)8 * cr + 32 + kPlaceCap;
         tr_place_self_kernel<false><<<(unsigned)n_regions, 256, lds2, st>>>(
-            n_rows, n_cols, band_width, cr, nreg, ptr, region_base, ent, tab, gcur, desc, nullptr,
-            (unsigned char *)t_rec, rec_unit);
+            n_rows, n_cols, band_width, cr, nreg, ptr, region_base, ent, tab, desc, nullptr, (unsigned char *)t_rec,
+            rec_unit);
     }
     GRF_CHECK_LAUNCH("tr_place_self_kernel");
     return GRF_OK;
@@ -1268,22 +1181,14 @@ int32_t grf_phi_row_shifts_stats(int64_t n_rows, const void *stats, float *maxab
     float *row_max, *wg_max;
     double *row_sum;
     row_stats_layout(const_cast<void *>(stats), n_rows, row_max, row_sum, wg_max);
-    const int64_t nwg = cdiv<int64_t>(n_rows, 4);
-    tr_maxabs_kernel<<<1, 1024, 0, st>>>(nwg, wg_max, maxabs);
-    GRF_CHECK_LAUNCH("tr_maxabs_kernel");
-    tr_rowshift_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 256), 256, 0, st>>>(n_rows, row_max, row_sum, maxabs,
-                                                                            row_shift);
-    GRF_CHECK_LAUNCH("tr_rowshift_kernel");
-    return GRF_OK;
+    return row_shifts_finish(st, n_rows, cdiv<int64_t>(n_rows, 4), wg_max, row_max, row_sum, maxabs, row_shift);
 }
 
-int32_t grf_phi_row_shifts_padded(int64_t n_rows, int64_t cap, const int32_t *cnt, const float *val, float *maxabs,
-                                  int32_t *row_shift, void *workspace, size_t workspace_bytes, grf_stream_t stream) {
-    GRF_REQUIRE(n_rows >= 0 && cap >= 1 && cnt && val && maxabs && row_shift && workspace, GRF_EINVAL,
-                "grf_phi_row_shifts_padded: bad arguments");
-    GRF_REQUIRE(workspace_bytes >= grf_phi_row_shifts_workspace_bytes(n_rows), GRF_EINVAL,
-                "grf_phi_row_shifts_padded: workspace too small");
-    hipStream_t st = S(stream);
+// grf_phi_row_shifts (cap = 0, cnt = NULL) and grf_phi_row_shifts_padded (ptr = NULL) after their own argument check
+static int32_t phi_row_shifts(const char *who, int64_t n_rows, const int64_t *ptr, int64_t cap, const int32_t *cnt,
+                              const float *val, float *maxabs, int32_t *row_shift, void *workspace,
+                              size_t workspace_bytes, hipStream_t st) {
+    GRF_REQUIRE(workspace_bytes >= grf_phi_row_shifts_workspace_bytes(n_rows), GRF_EINVAL, "%s: workspace too small", who);
     GRF_CHECK_HIP(hipMemsetAsync(maxabs, 0, sizeof(float), st));
     if (n_rows == 0) return GRF_OK;
     float *row_max, *wg_max;
@@ -1291,39 +1196,25 @@ int32_t grf_phi_row_shifts_padded(int64_t n_rows, int64_t cap, const int32_t *cn
     row_stats_layout(workspace, n_rows, row_max, row_sum, wg_max);
     const int64_t nwg = cdiv<int64_t>(n_rows, 4);
     GRF_REQUIRE_GRID(nwg, 256, "phi_row_stats_kernel");
-    phi_row_stats_kernel<<<(unsigned)nwg, 256, 0, st>>>(n_rows, nullptr, val, wg_max, row_max, row_sum, cap, cnt);
+    phi_row_stats_kernel<<<(unsigned)nwg, 256, 0, st>>>(n_rows, ptr, val, wg_max, row_max, row_sum, cap, cnt);
     GRF_CHECK_LAUNCH("phi_row_stats_kernel");
-    tr_maxabs_kernel<<<1, 1024, 0, st>>>(nwg, wg_max, maxabs);
-    GRF_CHECK_LAUNCH("tr_maxabs_kernel");
-    tr_rowshift_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 256), 256, 0, st>>>(n_rows, row_max, row_sum, maxabs,
-                                                                            row_shift);
-    GRF_CHECK_LAUNCH("tr_rowshift_kernel");
-    return GRF_OK;
+    return row_shifts_finish(st, n_rows, nwg, wg_max, row_max, row_sum, maxabs, row_shift);
+}
+
+int32_t grf_phi_row_shifts_padded(int64_t n_rows, int64_t cap, const int32_t *cnt, const float *val, float *maxabs,
+                                  int32_t *row_shift, void *workspace, size_t workspace_bytes, grf_stream_t stream) {
+    GRF_REQUIRE(n_rows >= 0 && cap >= 1 && cnt && val && maxabs && row_shift && workspace, GRF_EINVAL,
+                "grf_phi_row_shifts_padded: bad arguments");
+    return phi_row_shifts("grf_phi_row_shifts_padded", n_rows, nullptr, cap, cnt, val, maxabs, row_shift, workspace,
+                          workspace_bytes, S(stream));
 }
 
 int32_t grf_phi_row_shifts(int64_t n_rows, const int64_t *ptr, const float *val, float *maxabs, int32_t *row_shift,
                            void *workspace, size_t workspace_bytes, grf_stream_t stream) {
     GRF_REQUIRE(n_rows >= 0 && ptr && val && maxabs && row_shift && workspace, GRF_EINVAL,
                 "grf_phi_row_shifts: bad arguments");
-    GRF_REQUIRE(workspace_bytes >= grf_phi_row_shifts_workspace_bytes(n_rows), GRF_EINVAL,
-                "grf_phi_row_shifts: workspace too small");
-    hipStream_t st = S(stream);
-    GRF_CHECK_HIP(hipMemsetAsync(maxabs, 0, sizeof(float), st));
-    if (n_rows == 0) return GRF_OK;
-    char *w = (char *)workspace;
-    float *row_max = (float *)w;
-    double *row_sum = (double *)(w + tr_align((size_t)n_rows * 4));
-    float *wg_max = (float *)(w + tr_align((size_t)n_rows * 4) + tr_align((size_t)n_rows * 8));
-    const int64_t nwg = cdiv<int64_t>(n_rows, 4);
-    GRF_REQUIRE_GRID(nwg, 256, "phi_row_stats_kernel");
-    phi_row_stats_kernel<<<(unsigned)nwg, 256, 0, st>>>(n_rows, ptr, val, wg_max, row_max, row_sum);
-    GRF_CHECK_LAUNCH("phi_row_stats_kernel");
-    tr_maxabs_kernel<<<1, 1024, 0, st>>>(nwg, wg_max, maxabs);
-    GRF_CHECK_LAUNCH("tr_maxabs_kernel");
-    tr_rowshift_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 256), 256, 0, st>>>(n_rows, row_max, row_sum, maxabs,
-                                                                            row_shift);
-    GRF_CHECK_LAUNCH("tr_rowshift_kernel");
-    return GRF_OK;
+    return phi_row_shifts("grf_phi_row_shifts", n_rows, ptr, 0, nullptr, val, maxabs, row_shift, workspace,
+                          workspace_bytes, S(stream));
 }
 
 }  // extern "C"

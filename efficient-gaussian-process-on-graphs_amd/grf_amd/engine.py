@@ -193,6 +193,12 @@ def choose_rec_unit(nnz: int, n_rows: int, n_cols: int, band_width: int) -> int:
     return C.REC_LINE if per_bucket >= 8.0 else C.REC_PACKED
 
 
+def _phi_rec_unit(phi, nnz_bound, band_width: int) -> int:
+    """choose_rec_unit for a Phi whose nnz may not be on the host yet: its known nnz, else the caller's bound."""
+    nnz = phi.nnz if phi._nnz is not None or nnz_bound is None else nnz_bound
+    return choose_rec_unit(nnz, phi.n_rows, phi.n_cols, band_width)
+
+
 class DensePlanes:
     """The dense Phi as the split Gram's three bf16 planes (include/grf.h grf_split_planes): ``P`` uint8
     [n x row bytes] on the device, ``n`` rows, ``k_dim`` columns."""
@@ -571,14 +577,12 @@ class GRFEngine:
             if counted_ws is not None or not staged:
                 raise ValueError("self_count: the staged transpose counts its own buckets (no counted_ws)")
             if slots and not split and rec_unit is None and band_width > 4096:
-                u0 = choose_rec_unit(phi.nnz if phi._nnz is not None or nnz_bound is None else nnz_bound,
-                                     n_rows, n_cols, band_width)
+                u0 = _phi_rec_unit(phi, nnz_bound, band_width)
                 rec_unit = C.REC_SLOT if u0 == C.REC_PACKED else u0
             return self._transpose_self(phi, band_width, nnz_bound, rec_unit, t_desc, t_max, t_shift, split)
         ws = counted_ws if counted_ws is not None else self._ws(self.lib.grf_transpose_workspace_bytes(nbk))
         if rec_unit is None:
-            rec_unit = choose_rec_unit(phi.nnz if phi._nnz is not None or nnz_bound is None else nnz_bound,
-                                       n_rows, n_cols, band_width)
+            rec_unit = _phi_rec_unit(phi, nnz_bound, band_width)
         u = int(rec_unit)
         C.check(self.lib.grf_transpose_banded_plan(n_rows, n_cols, band_width, u, _p(phi.ptr), _p(phi.idx),
                                                    _p(t_desc), int(counted_ws is not None), _p(ws), ws.numel(),
@@ -625,8 +629,7 @@ class GRFEngine:
         n_rows, n_cols = phi.n_rows, phi.n_cols
         nnz = int(nnz_bound) if nnz_bound is not None else phi.nnz
         if rec_unit is None:
-            rec_unit = choose_rec_unit(phi.nnz if phi._nnz is not None or nnz_bound is None else nnz_bound,
-                                       n_rows, n_cols, band_width)
+            rec_unit = _phi_rec_unit(phi, nnz_bound, band_width)
         u = int(rec_unit)
         # the Gram addresses a band's records with 32-bit byte offsets: bound one band's slabs
         row_cap = min(n_cols, max(1, -(-nnz // max(n_rows, 1))))

@@ -663,3 +663,17 @@ def geometry_cases():
 
 def bands41_case():
     return random_case("n2600_W64", 2600, 64, 0.004, 11, empty_rows=(5, 2599))
+
+
+def dense128_case(seed=13):
+    """n = 640 at W = 128 with band 0 dense: rows 0..127 hold all 640 columns, every other row 3 random ones.
+    Each 16-row binning workgroup of band 0 holds 10240 entries (above the 8192 it can keep in LDS) and each of
+    band 0's five 128-column regions has a 98304-byte line / packed image and 95232 bytes of slot overflow pairs
+    (above the 48 KiB image cap), so the device transposes take their oversized-region paths there while bands
+    1..4 stay on the LDS paths in the same launch."""
+    rng = np.random.default_rng(seed)
+    n = 640
+    rows = [(np.arange(n, dtype=np.int32), _values(rng, n)) for _ in range(128)]
+    for _ in range(128, n):
+        rows.append((np.sort(rng.choice(n, 3, replace=False)).astype(np.int32), _values(rng, 3)))
+    return Case("dense128_W128", csr(n, n, rows), 128)

@@ -104,7 +104,7 @@ _CASES = {}
 def _case(name):
     if not _CASES:
         for c in G.geometry_cases() + [G.tie_case(), G.hub_case(), G.probe_case(4096), G.probe_case(8192),
-                                       G.bands41_case()]:
+                                       G.bands41_case(), G.dense128_case()]:
             _CASES[c.name] = c
     return _CASES[name]
 
@@ -562,7 +562,8 @@ MODES = {"atomic": dict(staged=False, self_count=False), "staged": dict(staged=T
 
 
 @pytest.mark.parametrize("mode", list(MODES))
-@pytest.mark.parametrize("name", ["n1_W64", "n65_W64", "n130_W64", "n400_W192", "n130_down40", "hub4100"])
+@pytest.mark.parametrize("name", ["n1_W64", "n65_W64", "n130_W64", "n400_W192", "n130_down40", "hub4100",
+                                  "dense128_W128"])
 def test_device_transposes_match_host_built(eng, name, mode):
     """engine.transpose_banded in every fill: the same pairs and the same multiset of (row offset, value bits) per
     bucket as the host-built transpose, t_split equal where it is non-zero, the rule's shifts on decided rows

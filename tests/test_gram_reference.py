@@ -255,3 +255,22 @@ def test_geometry_cases_hold_their_edges(cases):
         assert (G.row_lengths(by[name].P) == 0).any(), name
     b = G.bands41_case()
     assert -(-b.n // b.W) == 41
+
+
+def test_dense128_case_exceeds_the_lds_caps():
+    """dense128_W128 holds what it is there for: every 16-row binning workgroup of band 0 above the 8192 entries kept in
+    LDS, every 128-column region of band 0 above the 48 KiB image cap in the line and packed layouts and in the slot
+    layout's overflow pairs, bands 1..4 far below both, and every row's shift decided."""
+    c = G.dense128_case()
+    n, W, cr = c.n, c.W, 128
+    per_wg = np.add.reduceat(G.row_lengths(c.P), np.arange(0, n, 16))
+    assert np.all(per_wg[:W // 16] == 10240) and per_wg[W // 16:].max() <= 48
+    nb = -(-n // W)
+    for build, unit in ((G.transpose_line_ref, G.REC_LINE), (G.transpose_packed_ref, G.REC_PACKED)):
+        first = build(c.P, W)[0][0::2].astype(np.int64)                  # first unit of every bucket, then the total
+        img = (first[cr::cr][:nb * (n // cr)] - first[0:nb * n:cr]) * unit
+        assert np.all(img[:n // cr] == 98304) and img[n // cr:].max() < 48 * 1024, (unit, img)
+    pairs = G.transpose_slot_ref(c.P, W)[0][1:2 * nb * n:2].astype(np.int64)
+    ovf = (np.maximum(pairs - 2, 0) * 12).reshape(nb * (n // cr), cr).sum(axis=1)
+    assert np.all(ovf[:n // cr] == 95232) and ovf[n // cr:].max() == 0
+    assert c.shifts[1].all()
