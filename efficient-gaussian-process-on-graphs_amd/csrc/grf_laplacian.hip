@@ -20,7 +20,14 @@ namespace grf {
 int32_t scan_counts_i32(int64_t n, const int32_t *cnt, int64_t *out, void *ws, size_t ws_bytes, hipStream_t st);
 size_t scan_ws_bytes(int64_t n);
 
-// numpy pairwise_sum_DOUBLE leaf (n <= 128)
+// ---------------------------------------------------- numpy's pairwise sum
+// pairwise_sum_DOUBLE is a recursion (runs of more than 128 values split at n2 = n / 2 - (n / 2) % 8, the
+// halves combined left + right) over leaves of at most 128 values.  Both are written once here: pw_leaf /
+// leaf8 (the leaf by one lane / by the 8 lanes of a group) and pw_recurse (the traversal); the serial sum,
+// the plan of a row length and the plan's evaluator are their clients.
+
+// the leaf (n <= 128) by one lane: eight accumulators r_j = a[j] + a[j + 8] + ... over the first n - n % 8
+// values, the fixed tree over them, then the tail in order
 __device__ inline double pw_leaf(const double *a, int64_t n) {
     if (n < 8) {
         double r = 0.0;
@@ -38,23 +45,51 @@ __device__ inline double pw_leaf(const double *a, int64_t n) {
     return res;
 }
 
-// The recursion's explicit stack lives in LDS (one per wave, used by lane 0 only): a per-lane array in
-// registers would be dynamically indexed, i.e. private (scratch) memory -- 2.5 KB per lane, which the runtime
-// must back for every wave the device can hold at each launch of every kernel reaching this code.
+// the leaf's tree ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) over the accumulators held by the 8
+// lanes j of a group (every lane of the wave calls it); the result in each of the 8 lanes
+// (r by reference: by value, hipcc kept lap_deg_group_kernel's 16 row values as one indexed 32-register
+// vector copied whole at every use -- 236 VGPRs and as many AGPRs, 1 wave per SIMD, against 82 VGPRs)
+__device__ __forceinline__ double tree8(const double &r, int j) {
+    const double r1 = __shfl_xor(r, 1, 64);
+    const double p01 = (j & 1) ? r1 + r : r + r1;      // (r0 + r1), (r2 + r3), ...
+    const double p23 = __shfl_xor(p01, 2, 64);
+    const double q = (j & 2) ? p23 + p01 : p01 + p23;  // ((r0 + r1) + (r2 + r3)), ...
+    const double q4 = __shfl_xor(q, 4, 64);
+    return (j & 4) ? q4 + q : q + q4;
+}
+
+// the leaf (n <= 128) by the 8 lanes j of a group, lane j owning r_j; the sum in each of the 8 lanes
+// (n < 8: the accumulators and so the tree are +0.0, numpy's `res = 0.` before the tail from a[0])
+__device__ __forceinline__ double leaf8(const double *a, int32_t n, int j) {
+    const int32_t nb = n - (n % 8);
+    double r = 0.0;
+    if (j < nb) {
+        r = a[j];
+        for (int32_t q = 8 + j; q < nb; q += 8) r += a[q];
+    }
+    double res = tree8(r, j);
+    for (int32_t t = nb; t < n; ++t) res += a[t];
+    return res;
+}
+
+// The recursion, unrolled onto the explicit stack `st` (kPwDepth frames), post-order: leaf(off, m) gives
+// the value of a run a[off, off + m) of at most 128 values, join(left, right) that of a split run.
 // Depth: a frame of m > 128 values splits into halves of <= m / 2 + 8, so 64 frames cover any int64 n.
+// On the device the stack lives in LDS (one per wave, used by lane 0 only): a per-lane array in registers
+// would be dynamically indexed, i.e. private (scratch) memory -- 2.5 KB per lane, which the runtime must
+// back for every wave the device can hold at each launch of every kernel reaching this code.
 constexpr int kPwDepth = 64;
 struct PwFrame { int64_t off, n; double left; int32_t state; };
 
-// numpy pairwise_sum_DOUBLE, recursion unrolled onto the explicit stack `st`
-__device__ double np_pairwise(const double *a, int64_t n, PwFrame *st) {
-    if (n <= 128) return pw_leaf(a, n);
+template <typename Leaf, typename Join>
+__host__ __device__ inline double pw_recurse(int64_t n, PwFrame *st, Leaf leaf, Join join) {
     int sp = 0;
     st[0] = {0, n, 0.0, 0};
     double ret = 0.0;
     while (sp >= 0) {
         PwFrame &f = st[sp];
         if (f.n <= 128) {
-            ret = pw_leaf(a + f.off, f.n);
+            ret = leaf(f.off, f.n);
             --sp;
             continue;
         }
@@ -70,242 +105,163 @@ __device__ double np_pairwise(const double *a, int64_t n, PwFrame *st) {
             st[sp + 1] = {f.off + n2, f.n - n2, 0.0, 0};
             ++sp;
         } else {
-            ret = f.left + ret;
+            ret = join(f.left, ret);
             --sp;
         }
     }
     return ret;
 }
 
-// numpy pairwise_sum_DOUBLE of a[0 .. n) by one wave, bit for bit: the recursion's leaves (runs
-// of <= 128 values, split points n2 = n/2 - (n/2) % 8) are listed by lane 0, summed by the 64 lanes
-// in parallel with the leaf's own 8-accumulator order, and combined by lane 0 in the recursion's
-// order.  `ws` is the wave's LDS: kPwLeaves leaves and the stack; longer inputs fall back to lane 0.
-// Every lane returns the sum.  (A hub row of thousands of entries, or a dense row, no longer
-// costs one lane thousands of dependent adds.)
+// the sum by one lane (rows of more leaves than a plan holds)
+__device__ double np_pairwise(const double *a, int64_t n, PwFrame *st) {
+    return pw_recurse(
+        n, st, [&](int64_t off, int64_t m) { return pw_leaf(a + off, m); }, [](double l, double r) { return l + r; });
+}
+
+// The recursion of one row length as data: its leaves left to right and, after each, how many joins the
+// post-order runs before the next leaf.  Built once per length (the host, for the rows of a dense matrix:
+// a kernel argument; lane 0 of a wave, for a long CSR row: in LDS) and evaluated by the 64 lanes.
+// The split rule first yields more than 64 leaves at n = 7689 and more than 128 at n = 15369 (some longer
+// rows fit again: 8192 values are 64 leaves).
+template <int CAP>
+struct PwPlan {
+    int32_t nl;                   // leaves (0: no plan)
+    int32_t off[CAP], len[CAP];   // leaf l: a[off, off + len)
+    int8_t joins[CAP];            // after leaf l's sum is pushed: that many times pop two, push (left + right)
+};
+
+// false: more than CAP leaves
+template <int CAP>
+__host__ __device__ inline bool pw_plan_build(int64_t n, PwPlan<CAP> &p, PwFrame *st) {
+    p.nl = 0;
+    pw_recurse(
+        n, st,
+        [&](int64_t off, int64_t m) {
+            if (p.nl < CAP) {
+                p.off[p.nl] = (int32_t)off;
+                p.len[p.nl] = (int32_t)m;
+                p.joins[p.nl] = 0;
+            }
+            ++p.nl;
+            return 0.0;
+        },
+        [&](double, double) {
+            if (p.nl <= CAP) ++p.joins[p.nl - 1];
+            return 0.0;
+        });
+    return p.nl <= CAP;
+}
+
+// numpy's pairwise sum of a[0 .. n) from the plan of n, by one wave: the 8 lanes of group l % 8 sum leaf l
+// (leaf8), lane 0 combines the leaf sums in the plan's order.  `sums` holds CAP doubles of the wave's LDS;
+// the combine's stack is its front (never more values on the stack than leaves pushed), not a per-lane
+// array, which would be private memory.  Every lane returns the sum.
+template <int CAP>
+__device__ double plan_row_sum(const double *a, const PwPlan<CAP> &plan, double *sums, int lane) {
+    const int g = lane >> 3, j = lane & 7;
+    for (int l0 = 0; l0 < plan.nl; l0 += 8) {
+        const int l = l0 + g;
+        const bool in = l < plan.nl;
+        const double res = leaf8(a + (in ? plan.off[l] : 0), in ? plan.len[l] : 0, j);
+        if (j == 0 && in) sums[l] = res;
+    }
+    __builtin_amdgcn_wave_barrier();
+    double d = 0.0;
+    if (lane == 0) {
+        int sp = -1;
+        for (int l = 0; l < plan.nl; ++l) {
+            sums[++sp] = sums[l];
+            for (int q = plan.joins[l]; q > 0; --q) {
+                const double rgt = sums[sp--];
+                sums[sp] = sums[sp] + rgt;
+            }
+        }
+        d = sums[0];
+    }
+    __builtin_amdgcn_wave_barrier();
+    return __shfl(d, 0, 64);
+}
+
+// Integer rows (unit or small integer weights: every graph the benches run): when every value is an
+// integer of magnitude <= 2^20 and one is nonzero, every partial sum of any order is an exact integer
+// (< 2^53), so the numpy recursion's result is the exact sum, whatever the order it is taken in
+// (bit-identical; a zero total is +0.0 either way).  Per-lane state over the lane's share of the row.
+struct IntSum {
+    bool integral = true, nonzero = false;
+    double s = 0.0;
+    __device__ void add(double v) {
+        integral = integral && v == rint(v) && fabs(v) <= 1048576.0;
+        nonzero = nonzero || v != 0.0;
+        s += v;
+    }
+    // the wave's row is such a row: its sum in every lane
+    __device__ bool exact(double &sum) const {
+        if (!(__all(integral) && __any(nonzero))) return false;
+        sum = wave_sum(s);
+        return true;
+    }
+};
+
+// numpy pairwise_sum_DOUBLE of a[0 .. n) by one wave, bit for bit, every lane returning the sum: an
+// integer row by its exact sum, rows of up to kPwLeaves leaves by the plan lane 0 builds in the wave's
+// LDS `ws`, longer rows by lane 0 alone.  (A hub row of thousands of entries, or a dense row, does not
+// cost one lane thousands of dependent adds.)  Its callers' rows are longer than one leaf; a shorter row
+// is a plan of one leaf.
 constexpr int kPwLeaves = 128;
-struct PwLeaf { int64_t off; int64_t n; double sum; };
-struct PwScratch {
-    PwLeaf leaf[kPwLeaves];
+struct PwWave {
+    PwPlan<kPwLeaves> plan;
+    double sums[kPwLeaves];
     PwFrame st[kPwDepth];
 };
 
-__device__ double wave_np_pairwise(const double *a, int64_t n, PwScratch *ws) {
+__device__ double wave_np_pairwise(const double *a, int64_t n, PwWave *ws) {
     const int lane = threadIdx.x & 63;
-    PwLeaf *leaf = ws->leaf;
-    PwFrame *st = ws->st;
-    if (n <= 128) {
-        // one leaf: lanes 0..7 own the accumulators r_j (a[j], a[j + 8], ...), then the fixed tree
-        double r = 0.0;
-        if (n < 8) {
-            double t = 0.0;
-            if (lane == 0)
-                for (int64_t i = 0; i < n; ++i) t += a[i];
-            return __shfl(t, 0, 64);
-        }
-        const int64_t nb = n - (n % 8);
-        if (lane < 8) {
-            r = a[lane];
-            for (int64_t i = 8 + lane; i < nb; i += 8) r += a[i];
-        }
-        const double r0 = __shfl(r, 0, 64), r1 = __shfl(r, 1, 64), r2 = __shfl(r, 2, 64), r3 = __shfl(r, 3, 64);
-        const double r4 = __shfl(r, 4, 64), r5 = __shfl(r, 5, 64), r6 = __shfl(r, 6, 64), r7 = __shfl(r, 7, 64);
-        double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-        for (int64_t i = nb; i < n; ++i) res += a[i];
-        return res;
-    }
-    // Integer rows (unit or small integer weights: every graph the benches run): when every value is an
-    // integer of magnitude <= 2^20 and one is nonzero, every partial sum of any order is an exact integer
-    // (< 2^51), so the numpy recursion's result is the exact sum -- taken here in one strided pass and a
-    // wave reduction (bit-identical; a zero total is +0.0 either way).  Otherwise the recursion below.
-    {
-        bool integral = true, nonzero = false;
-        double s = 0.0;
-        for (int64_t i = lane; i < n; i += 64) {
-            const double v = a[i];
-            integral = integral && v == rint(v) && fabs(v) <= 1048576.0;
-            nonzero = nonzero || v != 0.0;
-            s += v;
-        }
-        if (__all(integral) && __any(nonzero)) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            return s;
-        }
-    }
-    // list the leaves (lane 0, the recursion's explicit stack), left to right
-    int32_t nl = 0;
-    if (lane == 0) {
-        int sp = 0;
-        st[0].off = 0;
-        st[0].n = n;
-        while (sp >= 0) {
-            const int64_t o = st[sp].off, m = st[sp].n;
-            --sp;
-            if (m <= 128) {
-                if (nl < kPwLeaves) leaf[nl] = PwLeaf{o, m, 0.0};
-                ++nl;
-                continue;
-            }
-            int64_t n2 = m / 2;
-            n2 -= n2 % 8;
-            // push right then left: the left subtree's leaves come first
-            ++sp;
-            st[sp].off = o + n2;
-            st[sp].n = m - n2;
-            ++sp;
-            st[sp].off = o;
-            st[sp].n = n2;
-        }
-    }
-    nl = __shfl(nl, 0, 64);
+    IntSum is;
+    for (int64_t i = lane; i < n; i += 64) is.add(a[i]);
+    double s;
+    if (is.exact(s)) return s;
+    int planned = 0;
+    if (lane == 0) planned = pw_plan_build(n, ws->plan, ws->st);
+    planned = __shfl(planned, 0, 64);
     __builtin_amdgcn_wave_barrier();
-    if (nl > kPwLeaves) {
-        const double t = lane == 0 ? np_pairwise(a, n, st) : 0.0;
-        return __shfl(t, 0, 64);
-    }
-    for (int l = lane; l < nl; l += 64) leaf[l].sum = pw_leaf(a + leaf[l].off, leaf[l].n);
-    __builtin_amdgcn_wave_barrier();
-    // combine in the recursion's order (lane 0): the same stack machine with leaf sums in order
-    double total = 0.0;
-    if (lane == 0) {
-        int sp = 0, next = 0;
-        st[0] = {0, n, 0.0, 0};
-        double ret = 0.0;
-        while (sp >= 0) {
-            PwFrame &f = st[sp];
-            if (f.n <= 128) {
-                ret = leaf[next++].sum;
-                --sp;
-                continue;
-            }
-            int64_t n2 = f.n / 2;
-            n2 -= n2 % 8;
-            if (f.state == 0) {
-                f.state = 1;
-                st[sp + 1] = {0, n2, 0.0, 0};
-                ++sp;
-            } else if (f.state == 1) {
-                f.left = ret;
-                f.state = 2;
-                st[sp + 1] = {0, f.n - n2, 0.0, 0};
-                ++sp;
-            } else {
-                ret = f.left + ret;
-                --sp;
-            }
-        }
-        total = ret;
-    }
-    __builtin_amdgcn_wave_barrier();
-    return __shfl(total, 0, 64);
+    if (planned) return plan_row_sum(a, ws->plan, ws->sums, lane);
+    const double t = lane == 0 ? np_pairwise(a, n, ws->st) : 0.0;
+    return __shfl(t, 0, 64);
 }
 
 // ------------------------------------------------------------------- scipy
-// degrees a_ii... : deg = a0 + pairwise(rest) per row (np.add.reduceat), one wave per row
-__global__ __launch_bounds__(256) void lap_deg_kernel(int64_t n, const int64_t *ptr, const double *val, double *deg,
-                                                      double *dinv) {
-    __shared__ PwScratch leaves[4];
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const int64_t b = ptr[i], e = ptr[i + 1];
-    const double rest = e - b > 1 ? wave_np_pairwise(val + b + 1, e - b - 1, &leaves[threadIdx.x >> 6]) : 0.0;
-    if ((threadIdx.x & 63) == 0) {
-        const double d = e > b ? val[b] + rest : 0.0;
-        deg[i] = d;
-        const double v = 1.0 / sqrt(d);
-        dinv[i] = isinf(v) ? 0.0 : v;
-    }
-}
-
-// One row of D^-1/2 (D - A) D^-1/2 in scipy order, one wave per row (a power-law hub row of
-// thousands of entries is spread over the 64 lanes instead of serialising one thread).
-// The row's virtual sequence is A's entries in column order with the diagonal merged into an
-// explicit (i, i) entry (value d - a_ii) or inserted before the first column > i (value d);
-// sp.diags drops a zero diagonal, so d == 0 inserts nothing and an explicit a_ii stays -a_ii.
-// Every element is computed independently with the serial code's exact arithmetic
-// (u = (dinv_i v) dinv_j, exact zeros dropped), then compacted in order by ballot counts.
-// EMIT=false counts.
-template <bool EMIT>
-__global__ __launch_bounds__(256) void lap_row_kernel(int64_t n, const int64_t *ptr, const int32_t *idx,
-                                                      const double *val, const double *deg, const double *dinv,
-                                                      int32_t *cnt, const int64_t *l_ptr, int32_t *l_idx,
-                                                      double *l_val, int64_t l_cap) {
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const int lane = threadIdx.x & 63;
-    const double d = deg[i], di = dinv[i];
-    const int64_t b = ptr[i], e = ptr[i + 1];
-    // first entry with column >= i (columns ascending)
-    int64_t lo = b, hi = e;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (idx[mid] < i) lo = mid + 1;
-        else hi = mid;
-    }
-    const int64_t pd = lo - b;  // position of the diagonal in the virtual sequence
-    const bool has_diag = d != 0.0;
-    const bool expl = lo < e && idx[lo] == i;
-    const bool insert = has_diag && !expl;
-    const int64_t total = (e - b) + (insert ? 1 : 0);
-    int64_t out = EMIT ? l_ptr[i] : 0;
-    int32_t c = 0;
-    for (int64_t base = 0; base < total; base += 64) {
-        const int64_t k = base + lane;
-        bool keep = false;
-        int64_t col = 0;
-        double u = 0.0;
-        if (k < total) {
-            double v;
-            if (insert && k == pd) {
-                col = i;
-                v = d;
-            } else {
-                const int64_t a = b + ((insert && k > pd) ? k - 1 : k);
-                col = idx[a];
-                v = (has_diag && col == i) ? d - val[a] : 0.0 - val[a];
-            }
-            if (v != 0.0 && di != 0.0) {
-                const double t = di * v;
-                if (t != 0.0) {
-                    const double dj = dinv[col];
-                    if (dj != 0.0) {
-                        u = t * dj;
-                        keep = u != 0.0;
-                    }
-                }
-            }
-        }
-        const uint64_t m = __ballot(keep);
-        if (EMIT) {
-            const int64_t o = out + __popcll(m & ((1ull << lane) - 1ull));
-            if (keep && o < l_cap) {
-                l_idx[o] = (int32_t)col;
-                l_val[o] = u;
-            }
-            out += __popcll(m);
-        } else {
-            c += __popcll(m);
-        }
-    }
-    if (!EMIT && lane == 0) cnt[i] = c;
-}
-
-// ---------------------------------------------- scipy, eight rows per wave
 // Most rows of a sparse graph are short (C5: mean degree ~10): a wave per row leaves 50+ lanes
 // idle.  These kernels give each row a group of 8 lanes (8 rows per wave); rows too long for a
 // group (degree sums over more than one numpy leaf, or 64 entries and more) are done afterwards by
-// the whole wave.  Same arithmetic, same bits.  Each lane issues ALL its loads of a row at once
-// (then the neighbours' D^-1/2 at once): a row costs three dependent round trips (row bounds,
-// entries, neighbour scales) instead of one per entry tail element and per binary-search step
+// the whole wave (lap_deg_wave, lap_row_wave).  Same arithmetic, same bits.  Each lane issues ALL its
+// loads of a row at once (then the neighbours' D^-1/2 at once): a row costs three dependent round trips
+// (row bounds, entries, neighbour scales) instead of one per entry tail element and per binary-search step
 // (C5, 1M rows: 627 us for the three launches, latency-bound at ~0.1 TB/s).
 constexpr int kGroupRowMax = 64;
 constexpr int kLeafPer = 16;  // 128 (one numpy leaf) / 8 lanes
 
+// scipy's D^-1/2 entry: 1 / sqrt(d), inf -> 0
+__device__ __forceinline__ double scipy_dinv(double d) {
+    const double v = 1.0 / sqrt(d);
+    return isinf(v) ? 0.0 : v;
+}
+
+// the degree of a row of more than one entry by the whole wave: deg = a0 + pairwise(a[1 ..]) (np.add.reduceat)
+__device__ void lap_deg_wave(int64_t i, const int64_t *__restrict__ ptr, const double *__restrict__ val,
+                             double *__restrict__ deg, double *__restrict__ dinv, PwWave *ws) {
+    const int64_t b = ptr[i], e = ptr[i + 1];
+    const double rest = wave_np_pairwise(val + b + 1, e - b - 1, ws);
+    if ((threadIdx.x & 63) == 0) {
+        const double d = val[b] + rest;
+        deg[i] = d;
+        dinv[i] = scipy_dinv(d);
+    }
+}
+
 __global__ __launch_bounds__(256) void lap_deg_group_kernel(int64_t n, const int64_t *__restrict__ ptr,
                                                             const double *__restrict__ val, double *__restrict__ deg,
                                                             double *__restrict__ dinv) {
-    __shared__ PwScratch leaves[4];
+    __shared__ PwWave pw[4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 3, j = lane & 7;
     const int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * 8;
     if (r0 >= n) return;
@@ -319,8 +275,8 @@ __global__ __launch_bounds__(256) void lap_deg_group_kernel(int64_t n, const int
     const bool lng = m > 128;
     const int64_t mm = lng ? 0 : m;
     const double *a = val + b + 1;
-    // numpy's leaf: accumulator r_j = a[j] + a[j + 8] + ... over the first nb = mm - mm % 8 values,
-    // the fixed tree over r_0..r_7, then the tail a[nb ..) added in order (mm < 8: the tail alone from 0)
+    // numpy's leaf (leaf8) with the row's values loaded at once: accumulator r_j = a[j] + a[j + 8] + ... over
+    // the first nb = mm - mm % 8 values, the tree, then the tail a[nb ..) in order (mm < 8: the tail alone from 0)
     // (loads past the wave's longest row are skipped by a scalar branch: ER rows of ~20 entries issue 3)
     int64_t mw = mm;
 #pragma unroll
@@ -338,12 +294,7 @@ __global__ __launch_bounds__(256) void lap_deg_group_kernel(int64_t n, const int
 #pragma unroll
     for (int q = 1; q < kLeafPer; ++q)
         if (q < qmax && 8 * q + j < nb) r += x[q];
-    const double r1 = __shfl_xor(r, 1, 64);
-    const double p01 = (j & 1) ? r1 + r : r + r1;
-    const double p23 = __shfl_xor(p01, 2, 64);
-    const double qq = (j & 2) ? p23 + p01 : p01 + p23;
-    const double q4 = __shfl_xor(qq, 4, 64);
-    double res = (j & 4) ? q4 + qq : qq + q4;
+    double res = tree8(r, j);
     if (mm < 8) res = 0.0;  // (numpy: res = 0; res += a[i] for short inputs)
     // the tail value a[nb + j] is this lane's x[nb / 8]
     const int qt = (int)(nb >> 3);
@@ -360,29 +311,25 @@ __global__ __launch_bounds__(256) void lap_deg_group_kernel(int64_t n, const int
     if (j == 0 && i < n && !lng) {
         const double d = e > b ? a0 + res : 0.0;
         deg[i] = d;
-        const double v = 1.0 / sqrt(d);
-        dinv[i] = isinf(v) ? 0.0 : v;
+        dinv[i] = scipy_dinv(d);
     }
     uint64_t todo = __ballot(lng && j == 0 && i < n);
     while (todo) {  // long rows: the whole wave, one at a time
         const int gg = (__ffsll((long long)todo) - 1) >> 3;
         todo &= todo - 1;
-        const int64_t ii = r0 + gg, bb = ptr[ii], ee = ptr[ii + 1];
-        const double rr = wave_np_pairwise(val + bb + 1, ee - bb - 1, &leaves[wave]);
-        if (lane == 0) {
-            const double d = val[bb] + rr;
-            deg[ii] = d;
-            const double v = 1.0 / sqrt(d);
-            dinv[ii] = isinf(v) ? 0.0 : v;
-        }
+        lap_deg_wave(r0 + gg, ptr, val, deg, dinv, &pw[wave]);
     }
 }
 
-// One element of row i of D^-1/2 (D - A) D^-1/2 with the serial code's exact arithmetic, in two
-// halves so that the neighbour's D^-1/2 loads of several elements are in flight together:
-// lap_pre gives the scaled value t = di v and whether D^-1/2[col] is needed (else dropped),
-// lap_post the element u = t dj and whether it is kept (u != 0).  v = d - a_ii for an explicit
-// diagonal when d != 0, else 0 - a (sp.diags drops a zero diagonal); the inserted diagonal has v = d.
+// One row of D^-1/2 (D - A) D^-1/2 in scipy order.  The row's virtual sequence is A's entries in column
+// order with the diagonal merged into an explicit (i, i) entry (value d - a_ii) or inserted before the
+// first column > i (value d); sp.diags drops a zero diagonal, so d == 0 inserts nothing and an explicit
+// a_ii stays -a_ii.  Every element is computed independently with the serial code's exact arithmetic
+// (u = (dinv_i v) dinv_j, exact zeros dropped after each multiply), then compacted in order by ballot
+// counts.  The arithmetic is in two halves so that the neighbour's D^-1/2 loads of several elements are in
+// flight together: lap_entry gives an entry's v, lap_pre the scaled value t = di v and whether
+// D^-1/2[col] is needed (else dropped), lap_post the element u = t dj and whether it is kept (u != 0).
+__device__ __forceinline__ double lap_entry(bool merge, double d, double w) { return merge ? d - w : 0.0 - w; }
 __device__ __forceinline__ bool lap_pre(double v, double di, double &t) {
     if (v != 0.0 && di != 0.0) {
         t = di * v;
@@ -399,7 +346,7 @@ __device__ __forceinline__ bool lap_post(bool need, double t, double dj, double 
     return false;
 }
 
-// the row's virtual sequence (long rows, the whole wave): element k -> (column, scaled value, kept)
+// the row's virtual sequence (long rows, the whole wave): element k -> (column, value before the scales)
 struct LapRow {
     int64_t i, b, e, pd, total;
     double d, di;
@@ -410,19 +357,19 @@ struct LapRow {
         di = dinv[i];
         b = ptr[i];
         e = ptr[i + 1];
-        int64_t lo = b, hi = e;
+        int64_t lo = b, hi = e;  // first entry with column >= i (columns ascending)
         while (lo < hi) {
             const int64_t mid = (lo + hi) >> 1;
             if (idx[mid] < i) lo = mid + 1;
             else hi = mid;
         }
-        pd = lo - b;
+        pd = lo - b;  // position of the diagonal in the virtual sequence
         has_diag = d != 0.0;
         const bool expl = lo < e && idx[lo] == i;
         insert = has_diag && !expl;
         total = (e - b) + (insert ? 1 : 0);
     }
-    // element k's column and value before the neighbour scale (k < total)
+    // element k's column and value before the scales (k < total)
     __device__ void raw(int64_t k, const int32_t *idx, const double *val, int32_t &col, double &v) const {
         if (insert && k == pd) {
             col = (int32_t)i;
@@ -430,11 +377,54 @@ struct LapRow {
         } else {
             const int64_t a = b + ((insert && k > pd) ? k - 1 : k);
             col = idx[a];
-            const double w = val[a];
-            v = (has_diag && col == i) ? d - w : 0.0 - w;
+            v = lap_entry(has_diag && col == i, d, val[a]);
         }
     }
 };
+
+// a row of kGroupRowMax entries and more by the whole wave, 4 x 64 elements in flight per round (a power-law
+// hub row of thousands of entries is spread over the 64 lanes); EMIT = false counts
+template <bool EMIT>
+__device__ void lap_row_wave(int64_t row, const int64_t *__restrict__ ptr, const int32_t *__restrict__ idx,
+                             const double *__restrict__ val, const double *__restrict__ deg,
+                             const double *__restrict__ dinv, int32_t *__restrict__ cnt,
+                             const int64_t *__restrict__ l_ptr, int32_t *__restrict__ l_idx,
+                             double *__restrict__ l_val, int64_t l_cap) {
+    const int lane = threadIdx.x & 63;
+    LapRow W;
+    W.init(row, ptr, idx, deg, dinv);
+    int64_t o0 = EMIT ? l_ptr[W.i] : 0;
+    for (int64_t base = 0; base < W.total; base += 256) {
+        int32_t c4[4];
+        double t4[4], dj4[4];
+        bool n4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t k = base + 64 * u + lane;
+            double v = 0.0;
+            c4[u] = (int32_t)W.i;
+            if (k < W.total) W.raw(k, idx, val, c4[u], v);
+            n4[u] = k < W.total && lap_pre(v, W.di, t4[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) dj4[u] = dinv[n4[u] ? c4[u] : (int32_t)W.i];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            double uu;
+            const bool keep = lap_post(n4[u], t4[u], dj4[u], uu);
+            const uint64_t m = __ballot(keep);
+            if (EMIT) {
+                const int64_t o = o0 + __popcll(m & ((1ull << lane) - 1ull));
+                if (keep && o < l_cap) {
+                    l_idx[o] = c4[u];
+                    l_val[o] = uu;
+                }
+            }
+            o0 += __popcll(m);
+        }
+    }
+    if (!EMIT && lane == 0) cnt[W.i] = (int32_t)o0;
+}
 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void lap_row_group_kernel(int64_t n, const int64_t *__restrict__ ptr,
@@ -496,8 +486,7 @@ __global__ __launch_bounds__(256) void lap_row_group_kernel(int64_t n, const int
         dj[q] = 0.0;
         if (q < qmax) {
             const bool in = 8 * q + j < len;
-            const double v = (has_diag && col[q] == i) ? d - w[q] : 0.0 - w[q];
-            need[q] = in && lap_pre(v, di, t[q]);
+            need[q] = in && lap_pre(lap_entry(has_diag && col[q] == i, d, w[q]), di, t[q]);
             dj[q] = dinv[need[q] ? col[q] : (valid ? i : 0)];
         }
     }
@@ -535,42 +524,10 @@ __global__ __launch_bounds__(256) void lap_row_group_kernel(int64_t n, const int
         }
     }
     uint64_t todo = __ballot(lng && j == 0 && valid);
-    while (todo) {  // long rows: the whole wave, 4 x 64 elements in flight per round
+    while (todo) {  // long rows: the whole wave, one at a time
         const int gg = (__ffsll((long long)todo) - 1) >> 3;
         todo &= todo - 1;
-        LapRow W;
-        W.init(r0 + gg, ptr, idx, deg, dinv);
-        int64_t o0 = EMIT ? l_ptr[W.i] : 0;
-        for (int64_t base = 0; base < W.total; base += 256) {
-            int32_t c4[4];
-            double t4[4], dj4[4];
-            bool n4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t k = base + 64 * u + lane;
-                double v = 0.0;
-                c4[u] = (int32_t)W.i;
-                if (k < W.total) W.raw(k, idx, val, c4[u], v);
-                n4[u] = k < W.total && lap_pre(v, W.di, t4[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) dj4[u] = dinv[n4[u] ? c4[u] : (int32_t)W.i];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                double uu;
-                const bool keep = lap_post(n4[u], t4[u], dj4[u], uu);
-                const uint64_t m = __ballot(keep);
-                if (EMIT) {
-                    const int64_t o = o0 + __popcll(m & ((1ull << lane) - 1ull));
-                    if (keep && o < l_cap) {
-                        l_idx[o] = c4[u];
-                        l_val[o] = uu;
-                    }
-                }
-                o0 += __popcll(m);
-            }
-        }
-        if (!EMIT && lane == 0) cnt[W.i] = (int32_t)o0;
+        lap_row_wave<EMIT>(r0 + gg, ptr, idx, val, deg, dinv, cnt, l_ptr, l_idx, l_val, l_cap);
     }
 }
 
@@ -579,7 +536,7 @@ __global__ __launch_bounds__(256) void lap_row_group_kernel(int64_t n, const int
 //
 //  lapd_stage_kernel -- one wave per row, 16-B loads with 8 per lane in flight: the degree (numpy's
 //    pairwise sum: rows of integer values take the exact strided sum, any other row the recursion's
-//    plan below), D^-1/2, and the row's structural nonzeros (w != 0) in column order, the first
+//    plan), D^-1/2, and the row's structural nonzeros (w != 0) in column order, the first
 //    kLapdCap of them staged as (column, w) pairs.  It also zeroes the next launch's look-back words.
 //  lapd_emit_kernel -- tiles of 256 rows in ticket order: each row's Laplacian nonzeros from its staged
 //    pairs and the diagonal (one thread per row; a row with more than kLapdCap structural nonzeros is
@@ -595,100 +552,10 @@ __global__ __launch_bounds__(256) void lap_row_group_kernel(int64_t n, const int
 // diagonal can be stored -- the CSR is the np.flatnonzero order of the dense L (sampler.py:22-28).
 constexpr int kLapdCap = 127;  // staged structural nonzeros per row (+ the diagonal: two 64-lane rounds)
 
-// numpy's pairwise sum of a dense row, leaves and combine order from the host-built plan (all rows
-// have the same length): the 8 lanes of group l % 8 sum leaf l with numpy's accumulators r_j = a[j],
-// a[j + 8], ..., folded ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) plus the leaf's tail; lane 0
-// combines the leaf sums with the recorded post-order program.  Every lane returns the sum.
-constexpr int kPwPlanLeaves = 64;  // rows of up to 64 leaves: n <= 8192
-struct PwPlan {
-    int32_t nl;                      // leaves
-    int32_t nprog;                   // program tokens
-    int32_t off[kPwPlanLeaves];      // leaf l: a[off, off + len)
-    int32_t len[kPwPlanLeaves];
-    int8_t prog[2 * kPwPlanLeaves];  // post-order: >= 0 push leaf sum, -1 pop two, push (left + right)
-};
-
-static bool pw_plan_build(int64_t n, PwPlan &p) {
-    p.nl = 0;
-    p.nprog = 0;
-    if (n <= 128) return false;  // (one leaf: wave_np_pairwise's own path)
-    struct F { int64_t o, m; int state; };
-    F st[64];
-    int sp = 0;
-    st[0] = {0, n, 0};
-    while (sp >= 0) {
-        F &f = st[sp];
-        if (f.m <= 128) {
-            if (p.nl >= kPwPlanLeaves) return false;
-            p.off[p.nl] = (int32_t)f.o;
-            p.len[p.nl] = (int32_t)f.m;
-            p.prog[p.nprog++] = (int8_t)p.nl;
-            ++p.nl;
-            --sp;
-            continue;
-        }
-        int64_t n2 = f.m / 2;
-        n2 -= n2 % 8;
-        if (f.state == 0) {
-            f.state = 1;
-            st[sp + 1] = {f.o, n2, 0};
-            ++sp;
-        } else if (f.state == 1) {
-            f.state = 2;
-            st[sp + 1] = {f.o + n2, f.m - n2, 0};
-            ++sp;
-        } else {
-            p.prog[p.nprog++] = -1;
-            --sp;
-        }
-    }
-    return true;
-}
-
-// (stk: the wave's LDS stack of the combine, kPwPlanLeaves doubles -- not a per-lane array, which would be
-// private memory)
-__device__ double plan_row_sum(const double *a, const PwPlan &plan, double *sums, double *stk, int lane) {
-    const int g = lane >> 3, j = lane & 7;
-    for (int l0 = 0; l0 < plan.nl; l0 += 8) {
-        const int l = l0 + g;
-        double r = 0.0;
-        int32_t off = 0, len = 0, nb = 0;
-        if (l < plan.nl) {
-            off = plan.off[l];
-            len = plan.len[l];
-            nb = len - (len % 8);  // (leaves of a split row hold >= 64 values)
-            r = a[off + j];
-            for (int32_t q = 8 + j; q < nb; q += 8) r += a[off + q];
-        }
-        const double r1 = __shfl_xor(r, 1, 64);
-        const double p01 = (j & 1) ? r1 + r : r + r1;       // (r0 + r1), (r2 + r3), ...
-        const double p23 = __shfl_xor(p01, 2, 64);
-        const double q = (j & 2) ? p23 + p01 : p01 + p23;  // ((r0 + r1) + (r2 + r3)), ...
-        const double q4 = __shfl_xor(q, 4, 64);
-        double res = (j & 4) ? q4 + q : q + q4;
-        if (j == 0 && l < plan.nl) {
-            for (int32_t t = nb; t < len; ++t) res += a[off + t];
-            sums[l] = res;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    double d = 0.0;
-    if (lane == 0) {
-        int sp = -1;
-        for (int t = 0; t < plan.nprog; ++t) {
-            const int tok = plan.prog[t];
-            if (tok >= 0) {
-                stk[++sp] = sums[tok];
-            } else {
-                const double rgt = stk[sp--];
-                stk[sp] = stk[sp] + rgt;
-            }
-        }
-        d = stk[0];
-    }
-    __builtin_amdgcn_wave_barrier();
-    return __shfl(d, 0, 64);
-}
+// The plan of the rows of a dense matrix (all of one length), built by the host and passed as a kernel
+// argument: rows of up to 64 leaves, which is every n < 7689 (and some beyond, see PwPlan); the other
+// lengths take wave_np_pairwise, each wave building its own plan or summing serially.
+constexpr int kPwPlanLeaves = 64;
 
 __device__ inline double lapd_value(int32_t mode, int64_t i, int64_t j, double w, const double *deg,
                                     const double *dinv) {
@@ -717,21 +584,11 @@ struct RowStager {
     }
 };
 
-struct IntSum {  // per-lane exact-integer-sum state of numpy's shortcut (wave_np_pairwise)
-    bool integral = true, nonzero = false;
-    double s = 0.0;
-    __device__ void add(double v) {
-        integral = integral && v == rint(v) && fabs(v) <= 1048576.0;
-        nonzero = nonzero || v != 0.0;
-        s += v;
-    }
-};
-
-__global__ __launch_bounds__(256) void lapd_stage_kernel(int64_t n, const double *W, int32_t mode, PwPlan plan,
-                                                         double *deg, double *dinv, int32_t *scnt, int32_t *scol,
-                                                         double *sval, uint64_t *flags, uint32_t *ticket) {
-    __shared__ double sums[4][kPwPlanLeaves], stk[4][kPwPlanLeaves];
-    __shared__ PwScratch leaves[4];
+__global__ __launch_bounds__(256) void lapd_stage_kernel(int64_t n, const double *W, int32_t mode,
+                                                         PwPlan<kPwPlanLeaves> plan, double *deg, double *dinv,
+                                                         int32_t *scnt, int32_t *scol, double *sval, uint64_t *flags,
+                                                         uint32_t *ticket) {
+    __shared__ PwWave pw[4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + wave;  // one wave per row
     if (i >= n) return;
@@ -770,12 +627,8 @@ __global__ __launch_bounds__(256) void lapd_stage_kernel(int64_t n, const double
         st.put(lane == 0 && v != 0.0, n - 1, v, false, 0, 0.0, lane);
     }
     double d;
-    if (__all(is.integral) && __any(is.nonzero)) {
-        // every partial sum of any order is an exact integer (< 2^53): the recursion's result, bit for bit
-        d = wave_sum(is.s);
-    } else {
-        d = plan.nl > 0 ? plan_row_sum(a, plan, sums[wave], stk[wave], lane) : wave_np_pairwise(a, n, &leaves[wave]);
-    }
+    if (!is.exact(d))
+        d = plan.nl > 0 ? plan_row_sum(a, plan, pw[wave].sums, lane) : wave_np_pairwise(a, n, &pw[wave]);
     if (lane == 0) {
         deg[i] = d;
         if (mode == GRF_LAP_NUMPY) dinv[i] = d > 0.0 ? 1.0 / sqrt(d) : 0.0;
@@ -922,8 +775,9 @@ __global__ __launch_bounds__(256) void lapd_emit_kernel(int64_t n, const double 
     }
     __syncthreads();
     const int32_t E = s_seg[R];
-    // the item e -> (row r, position k in the row's segment): upper bound in s_seg
-    auto locate = [&](int32_t e, int &r, int32_t &k) {
+    // The item e < E: its row r (upper bound in s_seg) and, when it is one of the row's staged pairs and not
+    // the diagonal item after them (the return value), the pair's column and Laplacian value.
+    auto item = [&](int32_t e, int &r, int64_t &col, double &u) {
         int lo = 0, hi = R;  // s_seg[lo] <= e < s_seg[hi]
 #pragma unroll
         for (int st = 0; st < 6; ++st) {
@@ -932,18 +786,20 @@ __global__ __launch_bounds__(256) void lapd_emit_kernel(int64_t n, const double 
             else hi = mid;
         }
         r = lo;
-        k = e - s_seg[lo];
+        const int32_t k = e - s_seg[lo];
+        if (k >= s_seg[lo + 1] - s_seg[lo] - 1) return false;
+        const int64_t i = r0 + r;
+        col = scol[i * kLapdCap + k];
+        u = lapd_value(mode, i, col, sval[i * kLapdCap + k], deg, dinv);
+        return true;
     };
     // pass 1a: the pairs (explicit diagonals flagged, nonzeros counted)
     for (int32_t e = tid; e < E; e += 256) {
         int r;
-        int32_t k;
-        locate(e, r, k);
-        const int64_t i = r0 + r;
-        const int32_t c = s_seg[r + 1] - s_seg[r] - 1;
-        if (k < c) {
-            const int64_t col = scol[i * kLapdCap + k];
-            const double u = lapd_value(mode, i, col, sval[i * kLapdCap + k], deg, dinv);
+        int64_t col;
+        double u;
+        if (item(e, r, col, u)) {
+            const int64_t i = r0 + r;
             if (col == i) s_expl[r] = 1;
             if (u != 0.0) {
                 atomicAdd(&s_cnt[r], 1);
@@ -992,20 +848,9 @@ __global__ __launch_bounds__(256) void lapd_emit_kernel(int64_t n, const double 
     for (int32_t e0 = 0; e0 < E; e0 += 256) {
         const int32_t e = e0 + tid;
         int r = 0;
-        int32_t k = 0;
-        bool nz = false;
         int64_t col = 0;
         double u = 0.0;
-        if (e < E) {
-            locate(e, r, k);
-            const int32_t c = s_seg[r + 1] - s_seg[r] - 1;
-            if (k < c) {
-                const int64_t i = r0 + r;
-                col = scol[i * kLapdCap + k];
-                u = lapd_value(mode, i, col, sval[i * kLapdCap + k], deg, dinv);
-                nz = u != 0.0;
-            }
-        }
+        const bool nz = e < E && item(e, r, col, u) && u != 0.0;
         const uint64_t m = __ballot(nz);
         __syncthreads();  // (the previous chunk's wave sums are read)
         if (lane == 0) s_wsum[wave] = __popcll(m);
@@ -1045,6 +890,32 @@ __global__ __launch_bounds__(256) void lapd_emit_kernel(int64_t n, const double 
     }
 }
 
+// ------------------------------------------------------------------- host
+// The workspaces' byte offsets, each the one source of its size function and of the entry's pointers.
+static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// CSR: [row counts, n i32 | scan scratch]
+struct LapCsrWs {
+    size_t scan, bytes;
+    explicit LapCsrWs(int64_t n)
+        : scan(al256((size_t)(n > 0 ? n : 1) * sizeof(int32_t))), bytes(scan + scan_ws_bytes(n)) {}
+};
+
+// dense: [dinv, n f64 | staged counts, n i32 | staged columns, n x cap i32 | staged values, n x cap f64 |
+// look-back words, n u64 | ticket (256 B)]
+struct LapDenseWs {
+    size_t scnt, scol, sval, flags, ticket, bytes;
+    explicit LapDenseWs(int64_t n) {
+        const size_t nn = (size_t)(n > 0 ? n : 1);
+        scnt = al256(nn * sizeof(double));
+        scol = scnt + al256(nn * sizeof(int32_t));
+        sval = scol + al256(nn * kLapdCap * sizeof(int32_t));
+        flags = sval + al256(nn * kLapdCap * sizeof(double));
+        ticket = flags + al256(nn * sizeof(uint64_t));
+        bytes = ticket + 256;
+    }
+};
+
 }  // namespace grf
 
 using namespace grf;
@@ -1052,19 +923,9 @@ using namespace grf;
 extern "C" {
 #pragma GCC visibility push(default)
 
-size_t grf_laplacian_csr_workspace_bytes(int64_t n) {
-    const size_t cnt_bytes = ((size_t)(n > 0 ? n : 1) * sizeof(int32_t) + 255) & ~(size_t)255;
-    return cnt_bytes + scan_ws_bytes(n);
-}
+size_t grf_laplacian_csr_workspace_bytes(int64_t n) { return LapCsrWs(n).bytes; }
 
-// dense workspace: dinv [n] f64 | staged counts [n] i32 | staged columns [n x cap] i32 | staged values
-// [n x cap] f64 | look-back words [n] u64 | ticket (256 B)
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t grf_laplacian_dense_workspace_bytes(int64_t n) {
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    return al256(nn * sizeof(double)) + al256(nn * sizeof(int32_t)) + al256(nn * kLapdCap * sizeof(int32_t)) +
-           al256(nn * kLapdCap * sizeof(double)) + al256(nn * sizeof(uint64_t)) + 256;
-}
+size_t grf_laplacian_dense_workspace_bytes(int64_t n) { return LapDenseWs(n).bytes; }
 
 int32_t grf_laplacian_csr(int64_t n, const int64_t *a_ptr, const int32_t *a_idx, const double *a_val, int32_t mode,
                           int64_t *l_ptr, int32_t *l_idx, double *l_val, int64_t l_cap, double *deg, double *dinv,
@@ -1072,39 +933,27 @@ int32_t grf_laplacian_csr(int64_t n, const int64_t *a_ptr, const int32_t *a_idx,
     GRF_REQUIRE(n >= 0 && a_ptr && l_ptr && deg && dinv, GRF_EINVAL, "grf_laplacian_csr: bad arguments");
     GRF_REQUIRE(mode == GRF_LAP_SCIPY, GRF_EUNSUPPORTED,
                 "grf_laplacian_csr: only GRF_LAP_SCIPY is defined for CSR input (got %d)", mode);
-    const size_t cnt_bytes = ((size_t)(n > 0 ? n : 1) * sizeof(int32_t) + 255) & ~(size_t)255;
-    GRF_REQUIRE(workspace_bytes >= cnt_bytes + scan_ws_bytes(n), GRF_EINVAL,
-                "grf_laplacian_csr: workspace too small (%zu < %zu)", workspace_bytes, cnt_bytes + scan_ws_bytes(n));
+    const LapCsrWs L(n);
+    GRF_REQUIRE(workspace_bytes >= L.bytes, GRF_EINVAL, "grf_laplacian_csr: workspace too small (%zu < %zu)",
+                workspace_bytes, L.bytes);
     hipStream_t st = S(stream);
     int32_t *cnt = (int32_t *)workspace;
     if (n == 0) {
         GRF_CHECK_HIP(hipMemsetAsync(l_ptr, 0, sizeof(int64_t), st));
         return GRF_OK;
     }
-    // eight rows per wave (GRF_LAP_WAVE_ROWS=1: one row per wave, for A/B runs)
-    static const bool wave_rows = [] {
-        const char *e = getenv("GRF_LAP_WAVE_ROWS");
-        return e && atoi(e) != 0;
-    }();
-    const unsigned gw = (unsigned)cdiv<int64_t>(n, wave_rows ? 4 : 32);
-    GRF_REQUIRE_GRID(gw, 256, "lap_deg_kernel");
-    if (wave_rows) lap_deg_kernel<<<gw, 256, 0, st>>>(n, a_ptr, a_val, deg, dinv);
-    else lap_deg_group_kernel<<<gw, 256, 0, st>>>(n, a_ptr, a_val, deg, dinv);
-    GRF_CHECK_LAUNCH("lap_deg_kernel");
-    if (wave_rows)
-        lap_row_kernel<false><<<gw, 256, 0, st>>>(n, a_ptr, a_idx, a_val, deg, dinv, cnt, nullptr, nullptr, nullptr, 0);
-    else
-        lap_row_group_kernel<false><<<gw, 256, 0, st>>>(n, a_ptr, a_idx, a_val, deg, dinv, cnt, nullptr, nullptr,
-                                                        nullptr, 0);
-    GRF_CHECK_LAUNCH("lap_row_kernel<count>");
-    int32_t rc = scan_counts_i32(n, cnt, l_ptr, (char *)workspace + cnt_bytes, workspace_bytes - cnt_bytes, st);
+    const unsigned gw = (unsigned)cdiv<int64_t>(n, 32);  // eight rows per wave
+    GRF_REQUIRE_GRID(gw, 256, "lap_deg_group_kernel");
+    lap_deg_group_kernel<<<gw, 256, 0, st>>>(n, a_ptr, a_val, deg, dinv);
+    GRF_CHECK_LAUNCH("lap_deg_group_kernel");
+    lap_row_group_kernel<false><<<gw, 256, 0, st>>>(n, a_ptr, a_idx, a_val, deg, dinv, cnt, nullptr, nullptr, nullptr,
+                                                    0);
+    GRF_CHECK_LAUNCH("lap_row_group_kernel<count>");
+    int32_t rc = scan_counts_i32(n, cnt, l_ptr, (char *)workspace + L.scan, workspace_bytes - L.scan, st);
     if (rc != GRF_OK) return rc;
-    if (wave_rows)
-        lap_row_kernel<true><<<gw, 256, 0, st>>>(n, a_ptr, a_idx, a_val, deg, dinv, nullptr, l_ptr, l_idx, l_val, l_cap);
-    else
-        lap_row_group_kernel<true><<<gw, 256, 0, st>>>(n, a_ptr, a_idx, a_val, deg, dinv, nullptr, l_ptr, l_idx, l_val,
-                                                       l_cap);
-    GRF_CHECK_LAUNCH("lap_row_kernel<fill>");
+    lap_row_group_kernel<true><<<gw, 256, 0, st>>>(n, a_ptr, a_idx, a_val, deg, dinv, nullptr, l_ptr, l_idx, l_val,
+                                                   l_cap);
+    GRF_CHECK_LAUNCH("lap_row_group_kernel<fill>");
     return GRF_OK;
 }
 
@@ -1116,28 +965,23 @@ int32_t grf_laplacian_dense(int64_t n, const double *W, int32_t mode, int64_t *l
                 GRF_EINVAL, "grf_laplacian_dense: bad mode %d", mode);
     GRF_REQUIRE(((uintptr_t)W & 7) == 0, GRF_EINVAL, "grf_laplacian_dense: W must be 8-byte aligned");
     GRF_REQUIRE(n < INT32_MAX, GRF_EINVAL, "grf_laplacian_dense: n must fit int32 column indices");
-    GRF_REQUIRE(workspace_bytes >= grf_laplacian_dense_workspace_bytes(n) && ((uintptr_t)workspace & 255) == 0,
-                GRF_EINVAL, "grf_laplacian_dense: workspace too small or not 256-byte aligned");
+    const LapDenseWs L(n);
+    GRF_REQUIRE(workspace_bytes >= L.bytes && ((uintptr_t)workspace & 255) == 0, GRF_EINVAL,
+                "grf_laplacian_dense: workspace too small or not 256-byte aligned");
     hipStream_t st = S(stream);
     if (n == 0) {
         GRF_CHECK_HIP(hipMemsetAsync(l_ptr, 0, sizeof(int64_t), st));
         return GRF_OK;
     }
-    const size_t nn = (size_t)n;
     char *w = (char *)workspace;
     double *dinv = (double *)w;
-    w += al256(nn * sizeof(double));
-    int32_t *scnt = (int32_t *)w;
-    w += al256(nn * sizeof(int32_t));
-    int32_t *scol = (int32_t *)w;
-    w += al256(nn * kLapdCap * sizeof(int32_t));
-    double *sval = (double *)w;
-    w += al256(nn * kLapdCap * sizeof(double));
-    uint64_t *flags = (uint64_t *)w;
-    w += al256(nn * sizeof(uint64_t));
-    uint32_t *ticket = (uint32_t *)w;
-    PwPlan plan;
-    if (!pw_plan_build(n, plan)) plan.nl = 0;
+    int32_t *scnt = (int32_t *)(w + L.scnt), *scol = (int32_t *)(w + L.scol);
+    double *sval = (double *)(w + L.sval);
+    uint64_t *flags = (uint64_t *)(w + L.flags);
+    uint32_t *ticket = (uint32_t *)(w + L.ticket);
+    PwPlan<kPwPlanLeaves> plan;
+    PwFrame frames[kPwDepth];
+    if (!pw_plan_build(n, plan, frames)) plan.nl = 0;
     const unsigned g = (unsigned)cdiv<int64_t>(n, 4);
     GRF_REQUIRE_GRID(g, 256, "lapd_stage_kernel");
     lapd_stage_kernel<<<g, 256, 0, st>>>(n, W, mode, plan, deg, dinv, scnt, scol, sval, flags, ticket);

@@ -10,6 +10,8 @@ Tolerances
     fixed-point sum rounded once): tests/test_gpu_gram_kernels.py holds it to its exact bits against the numpy
     restatement of tests/gram_reference.py.  The MFMA dense Gram is an fp32 FMA chain.
 """
+import functools
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -95,13 +97,14 @@ def test_laplacian_sparse_random(eng):
         assert same_csr(got, ref), seed
 
 
+@functools.lru_cache(maxsize=None)
 def _sparse_laplacian_cases():
     """CSR adjacencies (sorted columns, explicit entries kept as given) that reach every branch of the
     eight-rows-per-wave Laplacian kernels (grf_laplacian.hip): group rows of every length 0..63 and the
     leaf's tail sizes, whole-wave rows (>= 64 entries) and degree sums past one numpy leaf (> 129 entries),
     integral and non-integral weights, explicit / inserted / cancelling diagonals, zero and negative
     degrees, explicit zeros and -0.0 entries."""
-    r = np.random.default_rng(17)
+    r, r2 = np.random.default_rng(17), np.random.default_rng(18)  # (r2: the cases added later, r's stream kept)
     lengths = [0, 1, 2, 5, 7, 8, 9, 15, 16, 17, 31, 62, 63, 64, 65, 127, 128, 129, 130, 131, 200, 300, 700]
     cases = {}
     for name, unit in (("mixed_weighted", False), ("mixed_unit", True)):
@@ -132,15 +135,48 @@ def _sparse_laplacian_cases():
         elif kind == 4:  # an explicit diagonal inside the row
             cols = np.unique(np.append(cols, i))
             v = r.uniform(0.1, 2.0, len(cols))
+        if i in (13, 14):  # 129 / 130 entries led by an explicit diagonal: degree sums over 128 values (the
+            # group's one leaf) and 129 (the whole wave) together with the explicit-diagonal merge
+            cols = np.append(i, i + 1 + np.sort(r2.choice(n - i - 1, 128 + (i - 13), replace=False)))
+            v = r2.uniform(0.1, 2.0, len(cols))
         idx.extend(cols.tolist())
         val.extend(np.asarray(v, np.float64).tolist())
         ptr.append(len(idx))
     cases["signed_diag"] = sp.csr_matrix((np.asarray(val), np.asarray(idx, np.int32), np.asarray(ptr, np.int64)),
                                          shape=(n, n))
+    # the degree sum's tiers by numpy leaves (runs of <= 128 values; split n2 = n / 2 - (n / 2) % 8; the wave
+    # lists up to 128 leaves, longer rows are summed serially): hub rows with 15368 (128 leaves, the wave
+    # tier at capacity), 15369 (129 leaves, the shortest serial row) and 16500 (142 leaves) entries after the
+    # first, weighted, and a unit-weight hub of 16500 after the first (the exact integer sum in place of the
+    # serial tier); every other row has 0..9 entries
+    n = 16600
+    hubs = {3: (15368, False), 5000: (15369, False), 9001: (16500, False), 16599: (16500, True)}
+    ptr, idx, val = [0], [], []
+    for i in range(n):
+        m, unit = hubs.get(i, (None, False))
+        k = int(r2.integers(0, 10)) if m is None else m + 1
+        idx.extend(np.sort(r2.choice(n, k, replace=False)).tolist())
+        val.extend((np.ones(k) if unit else r2.uniform(0.1, 2.0, k)).tolist())
+        ptr.append(len(idx))
+    cases["hub_tiers"] = sp.csr_matrix((np.asarray(val), np.asarray(idx, np.int32), np.asarray(ptr, np.int64)),
+                                       shape=(n, n))
+    # one wave's eight rows of lengths 0, 63, 64, 200 weighted, 200 unit, 1, 129 weighted, 7: group rows and
+    # several whole-wave rows together, the long-row loop running more than once in the degree and the row
+    # kernels (n = 256: a row of 200 distinct columns needs more than 64 of them); the other rows are short
+    n = 256
+    wave = [(0, False), (63, False), (64, False), (200, False), (200, True), (1, False), (129, False), (7, False)]
+    ptr, idx, val = [0], [], []
+    for i in range(n):
+        k, unit = wave[i] if i < 8 else (int(r2.integers(0, 12)), False)
+        idx.extend(np.sort(r2.choice(n, k, replace=False)).tolist())
+        val.extend((np.ones(k) if unit else r2.uniform(0.1, 2.0, k)).tolist())
+        ptr.append(len(idx))
+    cases["mixed_wave"] = sp.csr_matrix((np.asarray(val), np.asarray(idx, np.int32), np.asarray(ptr, np.int64)),
+                                        shape=(n, n))
     return cases
 
 
-@pytest.mark.parametrize("name", ["mixed_weighted", "mixed_unit", "signed_diag"])
+@pytest.mark.parametrize("name", ["mixed_weighted", "mixed_unit", "signed_diag", "hub_tiers", "mixed_wave"])
 def test_laplacian_sparse_group_branches(eng, name):
     """The sparse (scipy-semantics) Laplacian bit-exact against the oracle, row pointer included, on rows
     of every length class and the diagonal / zero / sign cases above."""
@@ -203,18 +239,57 @@ def _dense_laplacian_cases():
     return cases
 
 
-@pytest.mark.parametrize("name", ["dense_weighted_odd", "unit_sparse_odd", "asym_signed", "cap_edges", "large_weighted"])
+_TINY_WEIGHTED = (1, 7, 8, 9, 15, 16, 127, 128, 129, 136, 137)
+
+
+def _tiny_weighted(n):
+    """Fully weighted symmetric W of the sizes around numpy's one leaf: the n < 8 loop, no tail / a tail of
+    1 / of 7, exactly one leaf (128) and the first two-leaf splits (129 = 64 + 65)."""
+    W = np.random.default_rng(100 + n).random((n, n))
+    return W + W.T
+
+
+def _assert_dense_laplacian(G, W, mode, ref_mode, tag):
+    ip, ix, dx = O.dense_to_walk_csr(W if ref_mode is None else O.laplacian_dense(W, ref_mode))
+    assert np.array_equal(G.indptr, ip), (tag, mode)
+    assert np.array_equal(G.indices, ix) and bit_equal(G.data, dx), (tag, mode)
+
+
+@pytest.mark.parametrize("name", ["dense_weighted_odd", "unit_sparse_odd", "asym_signed", "cap_edges", "large_weighted"]
+                         + [f"tiny_weighted_{n}" for n in _TINY_WEIGHTED])
 def test_laplacian_dense_stage_emit_branches(eng, name):
     """The one-read dense Laplacian (stage + look-back emit) bit-exact against the oracle in every mode,
     row pointer included, on inputs that take each branch: exact-integer and recursion degrees, the
     host plan and wave_np_pairwise, staged rows and rows re-read from W, rows at the stage's cap,
-    unaligned rows, zero / negative degrees, explicit and inserted diagonals."""
-    W = _dense_laplacian_cases()[name]
+    unaligned rows, zero / negative degrees, explicit and inserted diagonals, and the one-leaf and
+    first-split sizes."""
+    tiny = name.startswith("tiny_weighted_")
+    W = _tiny_weighted(int(name.rsplit("_", 1)[1])) if tiny else _dense_laplacian_cases()[name]
     for mode, ref_mode in ((1, 0), (2, 1), (3, 2), (4, None)):
-        G = eng.walk_matrix_dense(W, mode).to_scipy()
-        ip, ix, dx = O.dense_to_walk_csr(W if ref_mode is None else O.laplacian_dense(W, ref_mode))
-        assert np.array_equal(G.indptr, ip), (name, mode)
-        assert np.array_equal(G.indices, ix) and bit_equal(G.data, dx), (name, mode)
+        _assert_dense_laplacian(eng.walk_matrix_dense(W, mode).to_scipy(), W, mode, ref_mode, name)
+
+
+def test_laplacian_dense_workspace_reused_across_sizes(eng):
+    """grf_laplacian_dense on one workspace held across calls: n = 300, then n = 130 on other data, then
+    n = 300 again, each bit-exact against the oracle.  The stage kernel resets the ticket and the look-back
+    words that the emit launch after it uses, so what an earlier call left there does not matter."""
+    import torch
+    from grf_amd import _lib as C
+    from grf_amd.engine import DeviceCSR, _p
+    mode, ref_mode = 2, 1
+    Ws = [_tiny_weighted(300), _tiny_weighted(130), _tiny_weighted(300)]
+    ws = torch.empty(eng.lib.grf_laplacian_dense_workspace_bytes(300), dtype=torch.uint8, device=eng.device)
+    for call, W in enumerate(Ws):
+        n = W.shape[0]
+        Wt = torch.from_numpy(W).to(eng.device)
+        cap = n * n
+        lp = torch.empty(n + 1, dtype=torch.int64, device=eng.device)
+        li = torch.empty(cap, dtype=torch.int32, device=eng.device)
+        lv = torch.empty(cap, dtype=torch.float64, device=eng.device)
+        deg = torch.empty(n, dtype=torch.float64, device=eng.device)
+        C.check(eng.lib.grf_laplacian_dense(n, _p(Wt), mode, _p(lp), _p(li), _p(lv), cap, _p(deg), _p(ws), ws.numel(),
+                                            eng.stream), "grf_laplacian_dense")
+        _assert_dense_laplacian(DeviceCSR(n, n, lp, li, lv).to_scipy(), W, mode, ref_mode, call)
 
 
 # ---------------------------------------------------------------------- walks
