@@ -102,14 +102,17 @@ __global__ __launch_bounds__(256) void phi_merge_kernel(int64_t n_src, int64_t m
         end = pos + step_cnt[s * L + lane];
         fl = f[lane];
     }
-    int32_t head = pos < end ? step_idx[pos] : INT32_MAX;
+    // heads as unsigned: the mark of an exhausted row lies above every int32 node id, 2^31 - 1 included
+    // (INT32_MAX as the mark ended the merge at that node and dropped its entry)
+    constexpr uint32_t kDone = 0xffffffffu;
+    uint32_t head = pos < end ? (uint32_t)step_idx[pos] : kDone;
     int64_t out = 0;
     const int64_t obase = s * cap;
     for (;;) {
-        int32_t mn = head;
+        uint32_t mn = head;
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mn = min(mn, __shfl_xor(mn, off, 64));
-        if (mn == INT32_MAX) break;
+        for (int off = 32; off > 0; off >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, off, 64));
+        if (mn == kDone) break;
         const bool match = (head == mn);
         const double t = match ? fl * step_val[pos] : 0.0;
         uint64_t mask = __ballot(match);
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(256) void phi_merge_kernel(int64_t n_src, int64_t m
         }
         if (acc != 0.0) {
             if (lane == 0 && out < cap) {
-                phi_idx[obase + out] = mn;
+                phi_idx[obase + out] = (int32_t)mn;
                 phi_val[obase + out] = acc;
                 if (phi_val32) phi_val32[obase + out] = (float)acc;
             }
@@ -132,7 +135,7 @@ __global__ __launch_bounds__(256) void phi_merge_kernel(int64_t n_src, int64_t m
         }
         if (match) {
             ++pos;
-            head = pos < end ? step_idx[pos] : INT32_MAX;
+            head = pos < end ? (uint32_t)step_idx[pos] : kDone;
         }
     }
     if (lane == 0) phi_cnt[s] = (int32_t)(out < cap ? out : cap);
