@@ -18,7 +18,7 @@
 // band and a mirror pass copies the upper triangle down.
 //
 // Structure: two kernels produce every sparse K -- gram_sparse_kernel (a tile per workgroup; line, packed and slot
-// buckets) and gram_slot_pipe_kernel (persistent, software-pipelined over its tiles; slot buckets, column blocks).
+// buckets of record pairs, or line buckets of 16-byte record triples: the whole symmetric K) and gram_slot_pipe_kernel (persistent, software-pipelined over its tiles; slot buckets, column blocks).
 // They differ in how a wave's nonzeros and bucket descriptors reach its registers; from there both run the same
 // code, each piece written once: slot_buckets (a slot header's two virtual buckets), gram_stream_batch (scans,
 // bucket ids by gram_propagate_ids, window groups by gram_windows, the exact tail group) on a GramWaveState, and
@@ -61,6 +61,7 @@ typedef uint32_t uint4_v __attribute__((ext_vector_type(4)));
 constexpr int kChunk = 1024;  // stream positions covered by one bucket-id chunk (16 per lane)
 constexpr int kSub = 8;       // sub-bands of the transpose's split (grf_transpose_banded_self, t_split)
 constexpr int kPairBytesG = 12;  // one record pair
+constexpr int kTripleBytesG = 16;  // one record triple (GRF_REC_TRIPLES: line buckets, band_width <= 4096)
 // per wave: ids [kChunk], then tbase and aval for a batch of 64 * halves nonzeros
 constexpr int wave_state_bytes(int halves) { return kChunk + halves * 64 * 8; }
 
@@ -155,8 +156,8 @@ __device__ inline int gram_propagate_ids(unsigned char *bid, int carry, int lane
 // A wave's LDS state of one flattened batch stream, behind the workgroup's W accumulators.
 struct GramWaveState {
     unsigned char *bid;  // [kChunk] bucket of every stream position of the current chunk
-    int32_t *tbase;      // [64 kV] per bucket: byte offset of its first pair (from the band's first line)
-                         // - 12 * stream position
+    int32_t *tbase;      // [64 kV] per bucket: byte offset of its first record (from the band's first line)
+                         // - record bytes * stream position
     float *aval;         // [64 kV] per bucket: Phi[row,k]
 };
 
@@ -168,7 +169,7 @@ __device__ inline GramWaveState gram_wave_state(unsigned long long *acc, int64_t
 // What the windows of one tile's streams read and add to (see gram_sparse_kernel).
 struct GramStream {
     GramWaveState st;           // the wave's bucket ids and per-bucket bases and values (LDS)
-    __amdgpu_buffer_rsrc_t rec; // the band's record pairs, 12 bytes each (global, 32-bit offsets)
+    __amdgpu_buffer_rsrc_t rec; // the band's records, 12-byte pairs or 16-byte triples (global, 32-bit offsets)
     unsigned char *acc;         // tile accumulator (LDS), addressed by byte offset
     double S;                   // the row's fixed-point scale 2^sh
     int32_t safe;               // byte offset of a pair with finite values (masked positions read it)
@@ -180,12 +181,16 @@ struct __attribute__((aligned(4))) RecPair {
     float v0, v1;
 };
 
-// NW windows of 64 pairs starting at stream position w0 (chunk base c0, chunk end cend).
+// NW windows of 64 records starting at stream position w0 (chunk base c0, chunk end cend).
 // TAIL = 1: an exact tail group, NW = ceil((cend - w0) / 64) -- every window is full but the last, whose
-// positions >= cend are masked (they read a finite pair and add exactly 0 to distinct entries); 0: all full.
-template <int NW, int TAIL>
+// positions >= cend are masked (they read a finite record and add exactly 0 to distinct entries); 0: all full.
+// kRec: the record's bytes -- kPairBytesG: a pair, two products per position; kTripleBytesG: a triple {u32 c0 |
+// o1 << 12 | o2 << 22, 3 x f32} read with one 16-byte load, three products per position, the rows c0 and
+// (c0 & ~511) + o1 / o2 (accumulator byte offset = row << 3).
+template <int NW, int TAIL, int kRec>
 __device__ __forceinline__ void gram_windows(const GramStream &g, int32_t w0, int32_t c0, int32_t cend, int lane) {
     static_assert(TAIL == 0 || TAIL == 1, "only the last window of a group is ever masked");
+    static_assert(kRec == kPairBytesG || kRec == kTripleBytesG, "record pairs or triples");
     const bool last_ok = !TAIL || w0 + (NW - 1) * 64 + lane < cend;
     int m[NW];
 #pragma unroll
@@ -197,15 +202,34 @@ __device__ __forceinline__ void gram_windows(const GramStream &g, int32_t w0, in
     double sc[NW];
 #pragma unroll
     for (int u = 0; u < NW; ++u) {
-        pos[u] = g.st.tbase[m[u]] + 12 * (w0 + u * 64 + lane);
+        pos[u] = g.st.tbase[m[u]] + kRec * (w0 + u * 64 + lane);
         sc[u] = (double)g.st.aval[m[u]] * g.S;  // exact: a power-of-two scaling of an f32
     }
     if (TAIL) {
-        pos[NW - 1] = last_ok ? pos[NW - 1] : g.safe;  // the band's first pair (slots: slot 0's first pair): finite
+        pos[NW - 1] = last_ok ? pos[NW - 1] : g.safe;  // the band's first record (slots: slot 0's first pair): finite
         sc[NW - 1] = last_ok ? sc[NW - 1] : 0.0;
     }
     // phase order pinned: all descriptor reads, then all gathers in flight, then the adds
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (kRec == kTripleBytesG) {
+        uint4_v rec[NW];
+#pragma unroll
+        for (int u = 0; u < NW; ++u) rec[u] = __builtin_amdgcn_raw_buffer_load_b128(g.rec, (uint32_t)pos[u], 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < NW; ++u) {
+            const uint32_t cols = rec[u][0], base = cols & 0xe00u;
+            uint32_t c[3] = {(cols & 0xfffu) << 3, (base + ((cols >> 12) & 0x3ffu)) << 3, (base + (cols >> 22)) << 3};
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                if (TAIL && u == NW - 1) c[q] = last_ok ? c[q] : (uint32_t)(lane & 15) * 8u;
+                const long long v = fx_fma_round(sc[u], (double)__uint_as_float(rec[u][1 + q]));
+                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(g.acc + c[q]), (unsigned long long)v,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+        return;
+    }
     RecPair rec[NW];
 #pragma unroll
     for (int u = 0; u < NW; ++u) {
@@ -262,7 +286,7 @@ constexpr int kGramUnroll = 8;  // windows of gathers in flight per wave (4 and 
 // with the chunk), and the stream is gathered and added in groups of kGramUnroll windows of 64 pairs, the last
 // group with exactly the windows left (a full group would issue up to kGramUnroll - 1 all-masked windows of loads
 // and LDS adds per batch).
-template <int kV>
+template <int kV, int kRec = kPairBytesG>
 __device__ __forceinline__ void gram_stream_batch(const GramStream &gs, const int32_t *cnt, const int32_t *t0,
                                                   const float *av, int lane) {
     const GramWaveState &st = gs.st;
@@ -276,7 +300,7 @@ __device__ __forceinline__ void gram_stream_batch(const GramStream &gs, const in
     }
 #pragma unroll
     for (int h = 0; h < kV; ++h) {
-        st.tbase[h * 64 + lane] = t0[h] - 12 * excl[h];  // byte offset = tbase + 12 * position
+        st.tbase[h * 64 + lane] = t0[h] - kRec * excl[h];  // byte offset = tbase + record bytes * position
         st.aval[h * 64 + lane] = av[h];
     }
     int carry = 0;
@@ -299,18 +323,18 @@ __device__ __forceinline__ void gram_stream_batch(const GramStream &gs, const in
         __builtin_amdgcn_wave_barrier();
         int32_t w0 = c0;
         for (; w0 + 64 * kGramUnroll <= cend; w0 += 64 * kGramUnroll)
-            gram_windows<kGramUnroll, 0>(gs, w0, c0, cend, lane);
+            gram_windows<kGramUnroll, 0, kRec>(gs, w0, c0, cend, lane);
         if (w0 < cend) {
             static_assert(kGramUnroll == 8, "the tail switch lists 1 .. 8 windows");
             switch ((cend - w0 + 63) >> 6) {
-                case 1: gram_windows<1, 1>(gs, w0, c0, cend, lane); break;
-                case 2: gram_windows<2, 1>(gs, w0, c0, cend, lane); break;
-                case 3: gram_windows<3, 1>(gs, w0, c0, cend, lane); break;
-                case 4: gram_windows<4, 1>(gs, w0, c0, cend, lane); break;
-                case 5: gram_windows<5, 1>(gs, w0, c0, cend, lane); break;
-                case 6: gram_windows<6, 1>(gs, w0, c0, cend, lane); break;
-                case 7: gram_windows<7, 1>(gs, w0, c0, cend, lane); break;
-                default: gram_windows<8, 1>(gs, w0, c0, cend, lane); break;
+                case 1: gram_windows<1, 1, kRec>(gs, w0, c0, cend, lane); break;
+                case 2: gram_windows<2, 1, kRec>(gs, w0, c0, cend, lane); break;
+                case 3: gram_windows<3, 1, kRec>(gs, w0, c0, cend, lane); break;
+                case 4: gram_windows<4, 1, kRec>(gs, w0, c0, cend, lane); break;
+                case 5: gram_windows<5, 1, kRec>(gs, w0, c0, cend, lane); break;
+                case 6: gram_windows<6, 1, kRec>(gs, w0, c0, cend, lane); break;
+                case 7: gram_windows<7, 1, kRec>(gs, w0, c0, cend, lane); break;
+                default: gram_windows<8, 1, kRec>(gs, w0, c0, cend, lane); break;
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -417,7 +441,9 @@ struct GramTiles {
 // and its first two pairs in the 32-byte slot t_rec + 32 b, the other pairs at t_rec + ovf_base + 12 p --
 // so every nonzero contributes two virtual buckets (inline part, overflow part) to the wave's stream,
 // and a small bucket costs one line (header and pairs) instead of a descriptor line and a record line.
-template <int kWaves, int kHalves, bool kSlot>
+// kRec: the line buckets hold 12-byte pairs (kPairBytesG; also every packed and slot transpose) or 16-byte triples
+// (kTripleBytesG: one stream position per three entries, d.y counts triples).
+template <int kWaves, int kHalves, bool kSlot, int kRec>
 __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
     int64_t n_total, int64_t row_begin, GramTiles tl, int64_t t_begin, const int64_t *__restrict__ ptr,
     const int32_t *__restrict__ idx, const float *__restrict__ val, const uint2 *__restrict__ t_desc,
@@ -426,6 +452,7 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
     int64_t ovf_base, int32_t balance, const int32_t *__restrict__ row_cuts) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];  // [W]
     static_assert(!kSlot || kHalves == 1, "slot streams: 2 virtual buckets per nonzero, u8 ids <= 128");
+    static_assert(!kSlot || kRec == kPairBytesG, "slots hold pairs");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t W = tl.W;
     constexpr int kB = 64 * kHalves;        // nonzeros per wave batch
@@ -497,11 +524,11 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
                 const uint2 d = k >= 0 ? t_desc[boff + k] : make_uint2((uint32_t)line0, 0u);
                 // pairs of the sub-bands before the row's (diagonal tiles; capped: a dropped hub bucket has 0)
                 const int32_t skip = (dsub > 0 && k >= 0) ? min((int32_t)(t_split[(boff + k) * kSub + dsub] >> 1), (int32_t)d.y) : 0;
-                t0[h] = ((int32_t)d.x - line0) * unit + kPairBytesG * skip;  // first fetched byte within the band
-                cnt[h] = (int32_t)d.y - skip;                                   // pairs
+                t0[h] = ((int32_t)d.x - line0) * unit + kRec * skip;  // first fetched byte within the band
+                cnt[h] = (int32_t)d.y - skip;                            // records (pairs, or triples: never split)
             }
         }
-        gram_stream_batch<kV>(gs, cnt, t0, av, lane);
+        gram_stream_batch<kV, kRec>(gs, cnt, t0, av, lane);
     }
     if (kWaves > 1) __syncthreads();
     else __builtin_amdgcn_wave_barrier();
@@ -858,6 +885,7 @@ struct GramArgs {
     int64_t pad_cap;
     const int32_t *pad_cnt;
     int32_t unit;       // the banded transpose: GRF_REC_LINE / _PACKED / _SLOT
+    int32_t rec_kind;   // ... of GRF_REC_PAIRS, or GRF_REC_TRIPLES (line buckets, band_width <= 4096, no split)
     const uint32_t *t_desc;
     const void *t_rec;
     const void *t_split;      // sub-band split (or nullptr): read by symmetric launches only
@@ -885,6 +913,9 @@ static int32_t gram_check(const char *fn, bool args_ok, int32_t unit, const void
 // tiles [t_first, t_last) of one Gram call
 static int32_t gram_tiles_launch(const GramArgs &a, const GramTiles &tl, int64_t t_first, int64_t t_last) {
     const bool slot = a.unit == GRF_REC_SLOT;
+    GRF_REQUIRE(a.rec_kind == GRF_REC_PAIRS ||
+                    (a.rec_kind == GRF_REC_TRIPLES && a.unit == GRF_REC_LINE && tl.W <= 4096 && !a.t_split),
+                GRF_EINVAL, "gram: GRF_REC_TRIPLES needs line buckets, band_width <= 4096 and no t_split");
     const unsigned char *rec = reinterpret_cast<const unsigned char *>(a.t_rec);
     const int64_t ovf_base = slot ? 32 * tl.nb * a.n_total : 0;  // the overflow pairs follow the slots of all buckets
     if (slot) {
@@ -934,13 +965,14 @@ static int32_t gram_tiles_launch(const GramArgs &a, const GramTiles &tl, int64_t
     const int64_t max_tiles = ((1ll << 32) - 1) / (64 * waves);
     for (int64_t t0 = t_first; t0 < t_last; t0 += max_tiles) {
         const int64_t nt = (t_last - t0) < max_tiles ? (t_last - t0) : max_tiles;
-#define GRF_GRAM_LAUNCH(WV, H, SLOT)                                                                              \
-    gram_sparse_kernel<WV, H, SLOT><<<(unsigned)nt, 64 * WV, lds, a.st>>>(                                        \
+#define GRF_GRAM_LAUNCH(WV, H, SLOT, REC)                                                                         \
+    gram_sparse_kernel<WV, H, SLOT, REC><<<(unsigned)nt, 64 * WV, lds, a.st>>>(                                   \
         a.n_total, a.row_begin, tl, t0, a.ptr, a.idx, a.val, reinterpret_cast<const uint2 *>(a.t_desc), rec, a.unit, \
         a.rowshift, a.K, a.ldk, split, ovf_base, balance, a.row_cuts)
-        if (slot) GRF_GRAM_LAUNCH(8, 1, true);
-        else if (waves == 8) GRF_GRAM_LAUNCH(8, 1, false);
-        else GRF_GRAM_LAUNCH(4, 2, false);
+        if (slot) GRF_GRAM_LAUNCH(8, 1, true, kPairBytesG);
+        else if (waves == 8) GRF_GRAM_LAUNCH(8, 1, false, kPairBytesG);
+        else if (a.rec_kind == GRF_REC_TRIPLES) GRF_GRAM_LAUNCH(4, 2, false, kTripleBytesG);
+        else GRF_GRAM_LAUNCH(4, 2, false, kPairBytesG);
 #undef GRF_GRAM_LAUNCH
         GRF_CHECK_LAUNCH("gram_sparse_kernel");
     }
@@ -948,7 +980,7 @@ static int32_t gram_tiles_launch(const GramArgs &a, const GramTiles &tl, int64_t
 }
 
 // the rows [row_begin, row_end) of K = Phi Phi^T against Phi's own transpose, from the columns [k_begin, k_end)
-static int32_t gram_sparse_rows_impl(const char *fn, int64_t n_total, int64_t row_begin, int64_t row_end,
+static int32_t gram_sparse_rows_impl(const char *fn, int32_t rec_kind, int64_t n_total, int64_t row_begin, int64_t row_end,
                                      int64_t k_begin, int64_t k_end, const int64_t *ptr, const int32_t *idx,
                                      const float *val, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
                                      const void *t_rec, const int32_t *t_rowshift, float *K, int64_t ldk,
@@ -963,8 +995,8 @@ static int32_t gram_sparse_rows_impl(const char *fn, int64_t n_total, int64_t ro
     if (row_end == row_begin || n_total == 0) return GRF_OK;
     const GramTiles tl{row_end - row_begin, band_width, cdiv<int64_t>(n_total, band_width), false, (int32_t)k_begin,
                        (int32_t)k_end};
-    const GramArgs a{n_total,  row_begin, ptr,   idx,     val,        0,       nullptr,  //
-                     rec_unit, t_desc,    t_rec, nullptr, t_rowshift, nullptr, K, ldk, S(stream)};
+    const GramArgs a{n_total,  row_begin, ptr,    idx,   val,     0,          nullptr,  //
+                     rec_unit, rec_kind,  t_desc, t_rec, nullptr, t_rowshift, nullptr, K, ldk, S(stream)};
     return gram_tiles_launch(a, tl, 0, tl.total());
 }
 
@@ -972,12 +1004,20 @@ int32_t grf_gram_sparse(int64_t n_total, int64_t row_begin, int64_t row_end, con
                         const float *val, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
                         const void *t_rec, const int32_t *t_rowshift, float *K, int64_t ldk, void *workspace,
                         size_t workspace_bytes, grf_stream_t stream) {
-    return gram_sparse_rows_impl("grf_gram_sparse", n_total, row_begin, row_end, 0, n_total, ptr, idx, val, band_width,
-                                 rec_unit, t_desc, t_rec, t_rowshift, K, ldk, stream);
+    return gram_sparse_rows_impl("grf_gram_sparse", GRF_REC_PAIRS, n_total, row_begin, row_end, 0, n_total, ptr, idx, val,
+                                 band_width, rec_unit, t_desc, t_rec, t_rowshift, K, ldk, stream);
+}
+
+int32_t grf_gram_sparse_rec(int32_t rec_kind, int64_t n_total, int64_t row_begin, int64_t row_end, const int64_t *ptr,
+                            const int32_t *idx, const float *val, int64_t band_width, int32_t rec_unit,
+                            const uint32_t *t_desc, const void *t_rec, const int32_t *t_rowshift, float *K, int64_t ldk,
+                            grf_stream_t stream) {
+    return gram_sparse_rows_impl("grf_gram_sparse_rec", rec_kind, n_total, row_begin, row_end, 0, n_total, ptr, idx, val,
+                                 band_width, rec_unit, t_desc, t_rec, t_rowshift, K, ldk, stream);
 }
 
 // the whole K's tiles on and above the diagonal band, in parts [part_begin, part_end) of n_parts
-static int32_t gram_sparse_upper_impl(const char *fn, int64_t n_total, const int64_t *ptr, const int32_t *idx,
+static int32_t gram_sparse_upper_impl(const char *fn, int32_t rec_kind, int64_t n_total, const int64_t *ptr, const int32_t *idx,
                                       const float *val, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
                                       const void *t_rec, const void *t_split, const int32_t *t_rowshift,
                                       const int32_t *row_cuts, float *K, int64_t ldk, int32_t part_begin,
@@ -994,8 +1034,8 @@ static int32_t gram_sparse_upper_impl(const char *fn, int64_t n_total, const int
     const int64_t t0 = total * part_begin / n_parts, t1 = total * part_end / n_parts;
     if (t1 <= t0) return GRF_OK;
     GRF_REQUIRE(!row_cuts || rec_unit != GRF_REC_SLOT, GRF_EUNSUPPORTED, "%s: row cuts with slot buckets", fn);
-    const GramArgs a{n_total,  0,      ptr,   idx,     val,        0,        nullptr,  //
-                     rec_unit, t_desc, t_rec, t_split, t_rowshift, row_cuts, K, ldk, S(stream)};
+    const GramArgs a{n_total,  0,        ptr,    idx,   val,     0,          nullptr,  //
+                     rec_unit, rec_kind, t_desc, t_rec, t_split, t_rowshift, row_cuts, K, ldk, S(stream)};
     return gram_tiles_launch(a, tl, t0, t1);
 }
 
@@ -1003,7 +1043,7 @@ int32_t grf_gram_sparse_sym(int64_t n_total, const int64_t *ptr, const int32_t *
                             int64_t band_width, int32_t rec_unit, const uint32_t *t_desc, const void *t_rec,
                             const void *t_split, const int32_t *t_rowshift, float *K, int64_t ldk, void *workspace, size_t workspace_bytes,
                             grf_stream_t stream) {
-    int32_t rc = gram_sparse_upper_impl("grf_gram_sparse_sym", n_total, ptr, idx, val, band_width, rec_unit, t_desc,
+    int32_t rc = gram_sparse_upper_impl("grf_gram_sparse_sym", GRF_REC_PAIRS, n_total, ptr, idx, val, band_width, rec_unit, t_desc,
                                         t_rec, t_split, t_rowshift, nullptr, K, ldk, 0, 1, 1, false, stream);
     if (rc != GRF_OK || n_total == 0) return rc;
     return grf_gram_mirror(n_total, K, ldk, 0, stream);
@@ -1014,8 +1054,18 @@ int32_t grf_gram_sparse_upper_ex(int64_t n_total, const int64_t *ptr, const int3
                                  const void *t_split, const int32_t *t_rowshift, const int32_t *row_cuts, float *K,
                                  int64_t ldk, int32_t part_begin, int32_t part_end, int32_t n_parts, int32_t add_k,
                                  grf_stream_t stream) {
-    return gram_sparse_upper_impl("grf_gram_sparse_upper_ex", n_total, ptr, idx, val, band_width, rec_unit, t_desc,
+    return gram_sparse_upper_impl("grf_gram_sparse_upper_ex", GRF_REC_PAIRS, n_total, ptr, idx, val, band_width, rec_unit, t_desc,
                                   t_rec, t_split, t_rowshift, row_cuts, K, ldk, part_begin, part_end, n_parts,
+                                  add_k != 0, stream);
+}
+
+int32_t grf_gram_sparse_upper_rec(int32_t rec_kind, int64_t n_total, const int64_t *ptr, const int32_t *idx,
+                                  const float *val, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
+                                  const void *t_rec, const void *t_split, const int32_t *t_rowshift,
+                                  const int32_t *row_cuts, float *K, int64_t ldk, int32_t part_begin, int32_t part_end,
+                                  int32_t n_parts, int32_t add_k, grf_stream_t stream) {
+    return gram_sparse_upper_impl("grf_gram_sparse_upper_rec", rec_kind, n_total, ptr, idx, val, band_width, rec_unit,
+                                  t_desc, t_rec, t_split, t_rowshift, row_cuts, K, ldk, part_begin, part_end, n_parts,
                                   add_k != 0, stream);
 }
 
@@ -1089,7 +1139,7 @@ int32_t grf_gram_sparse_upper(int64_t n_total, const int64_t *ptr, const int32_t
                               const void *t_split, const int32_t *t_rowshift, float *K, int64_t ldk, int32_t part_begin,
                               int32_t part_end, int32_t n_parts, void *workspace, size_t workspace_bytes,
                               grf_stream_t stream) {
-    return gram_sparse_upper_impl("grf_gram_sparse_upper", n_total, ptr, idx, val, band_width, rec_unit, t_desc, t_rec,
+    return gram_sparse_upper_impl("grf_gram_sparse_upper", GRF_REC_PAIRS, n_total, ptr, idx, val, band_width, rec_unit, t_desc, t_rec,
                                   t_split, t_rowshift, nullptr, K, ldk, part_begin, part_end, n_parts, false, stream);
 }
 
@@ -1099,7 +1149,7 @@ int32_t grf_gram_sparse_upper_add(int64_t n_total, const int64_t *ptr, const int
                                   int32_t part_begin,
                                   int32_t part_end, int32_t n_parts, void *workspace, size_t workspace_bytes,
                                   grf_stream_t stream) {
-    return gram_sparse_upper_impl("grf_gram_sparse_upper_add", n_total, ptr, idx, val, band_width, rec_unit, t_desc,
+    return gram_sparse_upper_impl("grf_gram_sparse_upper_add", GRF_REC_PAIRS, n_total, ptr, idx, val, band_width, rec_unit, t_desc,
                                   t_rec, t_split, t_rowshift, nullptr, K, ldk, part_begin, part_end, n_parts, true,
                                   stream);
 }
@@ -1154,8 +1204,8 @@ static int32_t gram_sparse_cols_impl(const char *fn, int64_t n_cols, int64_t row
         if (r1 <= r0) return GRF_OK;
         GramTiles tl{r1 - r0, band_width, nb, sym, 0, (int32_t)n_cols};
         tl.t_rows = t_rows;
-        const GramArgs a{n_cols,   r0,     ptr,   idx,                     val,       pad_cap, pad_cnt,  //
-                         rec_unit, t_desc, t_rec, sym ? t_split : nullptr, row_shift, nullptr,
+        const GramArgs a{n_cols,   r0,            ptr,    idx,   val,                     pad_cap,   pad_cnt,  //
+                         rec_unit, GRF_REC_PAIRS, t_desc, t_rec, sym ? t_split : nullptr, row_shift, nullptr,
                          K + (r0 - row_begin) * ldk, ldk, st};
         return gram_tiles_launch(a, tl, 0, tl.total());
     };
@@ -1198,7 +1248,7 @@ int32_t grf_gram_sparse_kslice(int64_t n_total, int64_t row_begin, int64_t row_e
                                size_t workspace_bytes, grf_stream_t stream) {
     (void)workspace;
     (void)workspace_bytes;
-    return gram_sparse_rows_impl("grf_gram_sparse_kslice", n_total, row_begin, row_end, k_begin, k_end, ptr, idx, val,
+    return gram_sparse_rows_impl("grf_gram_sparse_kslice", GRF_REC_PAIRS, n_total, row_begin, row_end, k_begin, k_end, ptr, idx, val,
                                  band_width, rec_unit, t_desc, t_rec, t_rowshift, K, ldk, stream);
 }
 

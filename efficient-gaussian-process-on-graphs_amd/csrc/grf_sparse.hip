@@ -601,6 +601,15 @@ __global__ __launch_bounds__(256) void tr_place_kernel(int64_t n_rows, int64_t n
 // (3) tr_place_self counts the region's buckets in LDS, lays them out inside the slab (the unused
 // tail of a slab is never read: the Gram reads through the descriptors), writes their descriptors
 // and places the records as tr_place does.
+// Triples (unit = kTripleUnits, lines of 8 records): a triple closes with fewer than 3 entries only where its
+// bucket's entries run out of the two blocks e, e + 1 it may span, and the next triple then starts in block
+// e + 2 or later -- at most ceil(8 / 2) = 4 early closes per bucket (the bucket's last triple among them), each
+// leaving at most 2 places unused: 3 T <= c + 8, and lines = ceil(T / 8) <= (T + 7) / 8 <= (c + 29) / 24.  Over a
+// region, lines <= (E + 29 nb) / 24 <= (E + 8 nb) / 24 + nb + 1.  The worst case -- every entry of a bucket alone
+// in blocks 0, 2, 4, 6: c = T = 4, one line -- is within it ((4 + 8) / 24 + 1).
+constexpr int32_t kTripleUnits = -1;  // tr_region_units_kernel's unit for line buckets of record triples
+__host__ __device__ inline int64_t tr_triple_lines_bound(int64_t E, int64_t nb) { return (E + 8 * nb) / 24 + nb + 1; }
+
 __global__ __launch_bounds__(256) void tr_region_units_kernel(int64_t n_rows, int64_t n_cols, int64_t bw, int32_t cr,
                                                               int32_t nreg, int64_t n_regions, const int32_t *tab,
                                                               int32_t unit, int64_t *region_units) {
@@ -616,7 +625,10 @@ __global__ __launch_bounds__(256) void tr_region_units_kernel(int64_t n_rows, in
     E = wave_sum<int64_t>(E);
     const int64_t nb = R.n_buckets();
     if (lane == 0)
-        region_units[rg] = E == 0 ? 0 : unit == kPairBytes ? (E + nb + 1) / 2 : (6 * (E + nb)) / unit + nb + 1;
+        region_units[rg] = E == 0                ? 0
+                           : unit == kTripleUnits ? tr_triple_lines_bound(E, nb)
+                           : unit == kPairBytes   ? (E + nb + 1) / 2
+                                                  : (6 * (E + nb)) / unit + nb + 1;
 }
 
 struct RegionBaseOut {  // region_base[i] = first unit of region i; the total also as desc[nbk] (lo, hi)
@@ -731,6 +743,138 @@ __global__ __launch_bounds__(256) void tr_place_self_kernel(int64_t n_rows, int6
     place(image, true);
     __syncthreads();
     store_image(t_rec, U0 * unit, image, img);
+}
+
+// ---- 16-byte record triples (line buckets, band_width <= 4096): {u32 cols, f32 v0, f32 v1, f32 v2}, 8 per line,
+// cols = c0 | o1 << 12 | o2 << 22: c0 the first entry's row in the band, o1 / o2 the other rows as 10-bit
+// offsets from c0 & ~511, the start of c0's aligned block of kTriBlock rows.  A bucket's entries are laid out by
+// block (the band's up to 8 blocks in order, any order inside a block) and cut greedily: a triple whose first
+// entry lies in block e takes the following entries while they lie in block e or e + 1.  The triples of a bucket
+// and the slot (3 * triple + place) of every entry therefore follow from the bucket's block counts alone --
+// counted in pass 1, as the split placement counts its sub-bands -- and an entry's slot from its rank inside
+// its block: no sort.  Unused places are padding (row c0, +0.0): an exact 0 added in fixed point.
+constexpr int kTriBlock = 512, kTriBlocks = 8, kTripleBytes = 16;
+
+// Block e of a bucket as pass 2 needs it: its first `take` entries (by rank) fill the places the previous
+// block's last triple left free, from slot 3 * first - free; the others start triple `first`.
+struct TriBlock {
+    uint32_t first;  // the bucket's triples before this block's own
+    uint32_t info;   // entries | free << 16 | take << 18
+    __device__ uint32_t entries() const { return info & 0xffffu; }
+    __device__ uint32_t free_before() const { return (info >> 16) & 3u; }
+    __device__ uint32_t take() const { return info >> 18; }
+    // triples this block starts, and the places its last one leaves to the next block
+    __device__ uint32_t started() const { return (entries() - take() + 2u) / 3u; }
+    __device__ uint32_t free_after() const { return entries() > take() ? (3u - (entries() - take()) % 3u) % 3u : 0u; }
+};
+
+// The layout of one bucket from its block counts cnt[0 .. kTriBlocks): returns its triples; tb (or nullptr: the
+// count alone) receives the blocks' tables.
+__device__ __forceinline__ uint32_t tri_layout(const uint32_t *cnt, TriBlock *tb) {
+    uint32_t T = 0, free_ = 0;
+#pragma unroll
+    for (int e = 0; e < kTriBlocks; ++e) {
+        const uint32_t c = cnt[e], take = min(free_, c);
+        const TriBlock b{T, c | (free_ << 16) | (take << 18)};
+        if (tb) tb[e] = b;
+        T += b.started();
+        free_ = b.free_after();
+    }
+    return T;
+}
+
+// tr_place_self_kernel for triples: the same slabs, descriptors {first line, triples} and two passes over the
+// region's staged entries.  Who writes what, without a race between the three places of a record: every entry
+// stores its own value word; the cols word starts as 0 (zeroed image, or the zeroed lines of an oversized
+// region) and every entry ORs its own bit field into it atomically (place 0: c0; places 1 and 2: their offset);
+// after a barrier one pass over the block tables ORs the padding offsets c0 & 511 into the places a closed
+// triple left unused (their fields are still 0, their values the zero fill).  An oversized region (image above
+// kPlaceCap) runs the same code on t_rec itself, under the same per-block cursors.
+__global__ __launch_bounds__(256) void tr_place_self_triples_kernel(int64_t n_rows, int64_t n_cols, int64_t bw,
+                                                                    int32_t cr, int32_t nreg, const int64_t *ptr,
+                                                                    const int64_t *region_base, const uint2 *staging,
+                                                                    const int32_t *tab, uint2 *desc,
+                                                                    unsigned char *t_rec) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tps_smem[];
+    const int tid = threadIdx.x;
+    const TrRegion R = tr_region(xcd_contiguous_region(), n_rows, n_cols, bw, cr, nreg);
+    const int nbk_r = R.n_buckets();
+    const int64_t b0 = R.b0, U0 = region_base[R.rg];
+    TriBlock *ltab = reinterpret_cast<TriBlock *>(tps_smem);                 // [cr * kTriBlocks]
+    uint32_t *lcur = reinterpret_cast<uint32_t *>(ltab + cr * kTriBlocks);    // [cr * kTriBlocks] counts, then cursors
+    uint32_t *lline = lcur + cr * kTriBlocks;                                 // [cr] first byte of each bucket
+    int32_t *scratch = reinterpret_cast<int32_t *>(lline + cr);               // [8]
+    unsigned char *image = reinterpret_cast<unsigned char *>(scratch + 8);
+    // (the staged entry's low half is 8 * its row in the band)
+    auto row_of = [](uint32_t x) -> uint32_t { return (x & 0xffffu) >> 3; };
+    auto slot = [&](uint32_t x) -> uint32_t { return (x >> 16) * kTriBlocks + row_of(x) / kTriBlock; };
+    for (int i = tid; i < nbk_r * kTriBlocks; i += 256) lcur[i] = 0u;
+    __syncthreads();
+    // pass 1: the region's (bucket, block) counts
+    for_region_entries<4>(R, nreg, ptr, staging, tab, [&](uint2 x) { atomicAdd(&lcur[slot(x.x)], 1u); });
+    __syncthreads();
+    // bucket lines -> local offsets (thread t owns buckets [t * per, (t + 1) * per)), descriptors, block tables
+    const int per = (nbk_r + 255) / 256;
+    int32_t sum = 0;
+    for (int q = 0; q < per; ++q) {
+        const int i = tid * per + q;
+        if (i < nbk_r) sum += (int32_t)((tri_layout(lcur + i * kTriBlocks, nullptr) + 7u) / 8u);
+    }
+    int32_t total;
+    int32_t run_u = block_exclusive_scan<int32_t>(sum, scratch, &total);
+    for (int q = 0; q < per; ++q) {
+        const int i = tid * per + q;
+        if (i < nbk_r) {
+            const uint32_t T = tri_layout(lcur + i * kTriBlocks, ltab + i * kTriBlocks);
+            desc[b0 + i] = make_uint2((uint32_t)(U0 + run_u), T);
+            lline[i] = (uint32_t)run_u * 128u;
+            run_u += (int32_t)((T + 7u) / 8u);
+#pragma unroll
+            for (int e = 0; e < kTriBlocks; ++e) lcur[i * kTriBlocks + e] = 0u;  // (the counts become cursors)
+        }
+    }
+    const int64_t img = (int64_t)total * 128;
+    if (img == 0) return;
+    const bool lds = img <= kPlaceCap;
+    unsigned char *region = t_rec + U0 * 128;
+    unsigned char *dst = lds ? image : region;
+    if (lds) {
+        zero_image(image, img);
+    } else {
+        for (int64_t i = tid; i < img / 16; i += 256) reinterpret_cast<uint4 *>(region)[i] = make_uint4(0u, 0u, 0u, 0u);
+        __threadfence();
+    }
+    __syncthreads();
+    // pass 2: place the entries (the region's entries come from L2: pass 1 just read them)
+    for_region_entries<4>(R, nreg, ptr, staging, tab, [&](uint2 x) {
+        const uint32_t kk = x.x >> 16, j = row_of(x.x), s = slot(x.x);
+        const uint32_t r = atomicAdd(&lcur[s], 1u);
+        const TriBlock b = ltab[s];
+        const bool own = r < b.take();  // in the previous block's last triple: offsets count from that block
+        const uint32_t sl = own ? 3u * b.first - b.free_before() + r : 3u * b.first + (r - b.take());
+        const uint32_t t = sl / 3u, pl = sl - 3u * t;
+        const uint32_t off = (j & (kTriBlock - 1)) + (own ? (uint32_t)kTriBlock : 0u);
+        uint32_t *rec = reinterpret_cast<uint32_t *>(dst + lline[kk] + (size_t)kTripleBytes * t);
+        rec[1 + pl] = x.y;
+        atomicOr(rec, pl == 0 ? j : off << (pl == 1 ? 12 : 22));
+    });
+    if (!lds) __threadfence();
+    __syncthreads();
+    // padding: the places a block's last triple keeps free after the next block took its share
+    for (int i = tid; i < nbk_r * kTriBlocks; i += 256) {
+        const TriBlock b = ltab[i];
+        if (b.started() == 0) continue;
+        const int e = i % kTriBlocks;
+        const uint32_t taken = e + 1 < kTriBlocks ? ltab[i + 1].take() : 0u, unused = b.free_after() - taken;
+        if (unused == 0) continue;
+        uint32_t *rec = reinterpret_cast<uint32_t *>(dst + lline[i / kTriBlocks] +
+                                                     (size_t)kTripleBytes * (b.first + b.started() - 1u));
+        const uint32_t o = atomicOr(rec, 0u) & (kTriBlock - 1);  // (c0 & 511: place 0's OR, before the barrier)
+        atomicOr(rec, unused == 2 ? (o << 12) | (o << 22) : o << 22);
+    }
+    if (!lds) return;
+    __syncthreads();
+    store_image(t_rec, U0 * 128, image, img);
 }
 
 // GRF_REC_SLOT: bucket b owns the 32-byte slot t_rec + 32 b = {u32 pairs, u32 first overflow pair,
@@ -1074,23 +1218,38 @@ int64_t grf_transpose_self_units_bound(int64_t n_rows, int64_t n_cols, int64_t b
     return (6 * (nnz + nbk)) / rec_unit + nbk + 2 * n_regions + 1;
 }
 
-int32_t grf_transpose_banded_self(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
-                                  const int64_t *ptr, const int32_t *idx, const float *val, uint32_t *t_desc,
-                                  void *t_split, void *t_rec, int64_t t_rec_bytes, float *t_maxabs, int32_t *t_rowshift,
-                                  void *workspace, size_t workspace_bytes, int64_t nnz, void *staging,
-                                  size_t staging_bytes, grf_stream_t stream) {
-    int32_t rc = tr_check("grf_transpose_banded_self",
+int64_t grf_transpose_self_triples_lines_bound(int64_t n_rows, int64_t n_cols, int64_t band_width, int64_t nnz) {
+    if (n_cols <= 0 || band_width <= 0) return 1;
+    const int64_t nb = cdiv<int64_t>(std::max<int64_t>(n_rows, 1), band_width), nbk = nb * n_cols;
+    // the sum of tr_triple_lines_bound over the regions, for any split of nnz entries
+    return tr_triple_lines_bound(nnz, nbk) + TrSelfWs(n_rows, n_cols, band_width).n_regions;
+}
+
+// grf_transpose_banded_self (rec_kind = GRF_REC_PAIRS) and grf_transpose_banded_self_rec after the latter's checks
+static int32_t transpose_banded_self(const char *who, int32_t rec_kind, int64_t n_rows, int64_t n_cols,
+                                     int64_t band_width, int32_t rec_unit, const int64_t *ptr, const int32_t *idx,
+                                     const float *val, uint32_t *t_desc, void *t_split, void *t_rec,
+                                     int64_t t_rec_bytes, float *t_maxabs, int32_t *t_rowshift, void *workspace,
+                                     size_t workspace_bytes, int64_t nnz, void *staging, size_t staging_bytes,
+                                     grf_stream_t stream) {
+    const bool triples = rec_kind == GRF_REC_TRIPLES;
+    int32_t rc = tr_check(who,
                           ptr && idx && val && t_desc && t_rec && t_maxabs && t_rowshift && t_rec_bytes >= 0 && staging &&
                               workspace,
                           n_rows, n_cols, band_width, rec_unit, t_rec, true, true, t_split != nullptr);
     if (rc != GRF_OK) return rc;
     const int64_t nb = cdiv<int64_t>(n_rows, band_width), nbk = nb * n_cols;
     const TrSelfWs ws(n_rows, n_cols, band_width);
-    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_self: workspace too small");
+    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "%s: workspace too small", who);
     const TrStaging sg(n_rows, n_cols, nnz);
-    GRF_REQUIRE(nnz >= 0 && staging_bytes >= sg.bytes, GRF_EINVAL, "grf_transpose_banded_self: staging too small");
-    GRF_REQUIRE(t_rec_bytes >= grf_transpose_self_units_bound(n_rows, n_cols, band_width, rec_unit, nnz) * rec_unit,
-                GRF_ECAPACITY, "grf_transpose_banded_self: t_rec too small for the region slabs");
+    GRF_REQUIRE(nnz >= 0 && staging_bytes >= sg.bytes, GRF_EINVAL, "%s: staging too small", who);
+    const int64_t units_bound = triples ? grf_transpose_self_triples_lines_bound(n_rows, n_cols, band_width, nnz)
+                                        : grf_transpose_self_units_bound(n_rows, n_cols, band_width, rec_unit, nnz);
+    GRF_REQUIRE(t_rec_bytes >= units_bound * rec_unit, GRF_ECAPACITY, "%s: t_rec too small for the region slabs", who);
+    // (triples: the block tables, block cursors and bucket offsets in LDS before the region's image)
+    const size_t lds_tri = (size_t)sg.cr * (kTriBlocks * (sizeof(TriBlock) + 4) + 4) + 32 + kPlaceCap;
+    GRF_REQUIRE(!triples || lds_tri <= 160 * 1024, GRF_EUNSUPPORTED, "%s: regions of %d columns do not fit the LDS tables",
+                who, sg.cr);
     hipStream_t st = S(stream);
     uint2 *desc = reinterpret_cast<uint2 *>(t_desc);
     GRF_CHECK_HIP(hipMemsetAsync(t_maxabs, 0, sizeof(float), st));
@@ -1098,7 +1257,7 @@ int32_t grf_transpose_banded_self(int64_t n_rows, int64_t n_cols, int64_t band_w
         GRF_CHECK_HIP(hipMemsetAsync(t_desc, 0, (size_t)(nbk + 1) * 8, st));
         return GRF_OK;
     }
-    GRF_REQUIRE(((uintptr_t)t_split & 15) == 0, GRF_EINVAL, "grf_transpose_banded_self: t_split must be 16-byte aligned");
+    GRF_REQUIRE(((uintptr_t)t_split & 15) == 0, GRF_EINVAL, "%s: t_split must be 16-byte aligned", who);
     char *w = (char *)workspace;
     int64_t *region_units = (int64_t *)(w + ws.region_units), *region_base = (int64_t *)(w + ws.region_base);
     const uint2 *ent = (const uint2 *)staging;
@@ -1110,13 +1269,21 @@ int32_t grf_transpose_banded_self(int64_t n_rows, int64_t n_cols, int64_t band_w
     GRF_REQUIRE_GRID(cdiv<int64_t>(n_regions, 4), 256, "tr_region_units_kernel");
     tr_region_units_kernel<<<(unsigned)cdiv<int64_t>(n_regions, 4), 256, 0, st>>>(n_rows, n_cols, band_width, cr, nreg,
                                                                                  n_regions, tab,
-                                                                                 rec_unit == GRF_REC_SLOT ? kPairBytes : rec_unit,
+                                                                                 triples                    ? kTripleUnits
+                                                                                 : rec_unit == GRF_REC_SLOT ? kPairBytes
+                                                                                                            : rec_unit,
                                                                                  region_units);
     GRF_CHECK_LAUNCH("tr_region_units_kernel");
     rc = scan_exclusive<int64_t>(n_regions, region_units, ScanIdentity{}, RegionBaseOut{region_base, desc + nbk},
                                  (int64_t *)(w + ws.scan), st);
     if (rc != GRF_OK) return rc;
     GRF_REQUIRE_GRID(n_regions, 256, "tr_place_self_kernel");
+    if (triples) {
+        tr_place_self_triples_kernel<<<(unsigned)n_regions, 256, lds_tri, st>>>(
+            n_rows, n_cols, band_width, cr, nreg, ptr, region_base, ent, tab, desc, (unsigned char *)t_rec);
+        GRF_CHECK_LAUNCH("tr_place_self_triples_kernel");
+        return GRF_OK;
+    }
     if (rec_unit == GRF_REC_SLOT) {
         const size_t lds2 = (size_t)8 * cr + 32 + kPlaceCap;
         tr_place_slots_kernel<<<(unsigned)n_regions, 256, lds2, st>>>(n_rows, n_cols, band_width, cr, nreg, nbk, ptr,
@@ -1137,6 +1304,33 @@ int32_t grf_transpose_banded_self(int64_t n_rows, int64_t n_cols, int64_t band_w
     }
     GRF_CHECK_LAUNCH("tr_place_self_kernel");
     return GRF_OK;
+}
+
+int32_t grf_transpose_banded_self(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
+                                  const int64_t *ptr, const int32_t *idx, const float *val, uint32_t *t_desc,
+                                  void *t_split, void *t_rec, int64_t t_rec_bytes, float *t_maxabs, int32_t *t_rowshift,
+                                  void *workspace, size_t workspace_bytes, int64_t nnz, void *staging,
+                                  size_t staging_bytes, grf_stream_t stream) {
+    return transpose_banded_self("grf_transpose_banded_self", GRF_REC_PAIRS, n_rows, n_cols, band_width, rec_unit, ptr,
+                                 idx, val, t_desc, t_split, t_rec, t_rec_bytes, t_maxabs, t_rowshift, workspace,
+                                 workspace_bytes, nnz, staging, staging_bytes, stream);
+}
+
+int32_t grf_transpose_banded_self_rec(int32_t rec_kind, int64_t n_rows, int64_t n_cols, int64_t band_width,
+                                      int32_t rec_unit, const int64_t *ptr, const int32_t *idx, const float *val,
+                                      uint32_t *t_desc, void *t_split, void *t_rec, int64_t t_rec_bytes,
+                                      float *t_maxabs, int32_t *t_rowshift, void *workspace, size_t workspace_bytes,
+                                      int64_t nnz, void *staging, size_t staging_bytes, grf_stream_t stream) {
+    const char *who = "grf_transpose_banded_self_rec";
+    GRF_REQUIRE(rec_kind == GRF_REC_PAIRS || rec_kind == GRF_REC_TRIPLES, GRF_EINVAL,
+                "%s: rec_kind must be GRF_REC_PAIRS or GRF_REC_TRIPLES", who);
+    // triples: 12 bits of row in the band, line buckets, block order instead of the sub-band split -- the other
+    // combinations are not built
+    GRF_REQUIRE(rec_kind == GRF_REC_PAIRS || (band_width <= 4096 && rec_unit == GRF_REC_LINE && !t_split), GRF_EINVAL,
+                "%s: GRF_REC_TRIPLES needs band_width <= 4096, GRF_REC_LINE and no t_split", who);
+    return transpose_banded_self(who, rec_kind, n_rows, n_cols, band_width, rec_unit, ptr, idx, val, t_desc, t_split,
+                                 t_rec, t_rec_bytes, t_maxabs, t_rowshift, workspace, workspace_bytes, nnz, staging,
+                                 staging_bytes, stream);
 }
 
 size_t grf_phi_row_shifts_workspace_bytes(int64_t n_rows) {

@@ -26,6 +26,7 @@ RNG_PCG64, RNG_PHILOX = 0, 1
 LOAD_CUMULATIVE, LOAD_NONCUMULATIVE, LOAD_ABLATION = 0, 1, 2
 NORM_DIV, NORM_MUL_RECIP = 0, 1
 REC_LINE, REC_PACKED, REC_SLOT = 128, 12, 32
+REC_PAIRS, REC_TRIPLES = 0, 1  # grf_rec_kind: 12-byte record pairs, or 16-byte triples (line buckets only)
 # grf_spgemm_*'s per-row path thresholds (include/grf.h GRF_SPGEMM_*): products sorted in LDS up to the first,
 # output entries per LDS accumulator of the larger rows, and the bounds of those rows' wave count
 SPGEMM_SORT_PRODUCTS, SPGEMM_ACC_SLOTS, SPGEMM_BIG_MIN_WAVES, SPGEMM_BIG_MAX_WAVES = 1024, 4096, 8, 256
@@ -105,6 +106,12 @@ SIGNATURES = {
     "grf_transpose_staging_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "grf_transpose_banded_self": (_i32, [_i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                          _sz, _i64, _vp, _sz, _vp]),
+    "grf_transpose_banded_self_rec": (_i32, [_i32, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                             _vp, _sz, _i64, _vp, _sz, _vp]),
+    "grf_transpose_self_triples_lines_bound": (_i64, [_i64, _i64, _i64, _i64]),
+    "grf_gram_sparse_rec": (_i32, [_i32, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "grf_gram_sparse_upper_rec": (_i32, [_i32, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                         _i32, _i32, _i32, _i32, _vp]),
     "grf_transpose_self_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "grf_transpose_self_units_bound": (_i64, [_i64, _i64, _i64, _i32, _i64]),
     "grf_csr_transpose_workspace_bytes": (_sz, [_i64, _i64, _i64]),

@@ -176,6 +176,9 @@ class Banded:
     # per bucket 8 uint16 entry offsets of its sub-bands (buckets laid out by sub-band; the symmetric
     # Gram's diagonal tiles start there), or None (records in arbitrary order within a bucket)
     t_split: Optional[torch.Tensor] = None
+    # C.REC_PAIRS, or C.REC_TRIPLES: line buckets of 16-byte triples {u32 c0 | o1 << 12 | o2 << 22, 3 x f32}
+    # (include/grf.h grf_rec_kind; t_desc then holds {first line, triples}); the whole-K and row Gram read both
+    rec_kind: int = C.REC_PAIRS
 
 
 def cols_band_width(rows: int, max_width: int = ROWS_BAND_WIDTH) -> int:
@@ -549,7 +552,8 @@ class GRFEngine:
     def transpose_banded(self, phi: DeviceCSR, band_width: int = DEFAULT_BAND_WIDTH,
                          counted_ws: Optional[torch.Tensor] = None, staged: Optional[bool] = None,
                          nnz_bound: Optional[int] = None, rec_unit: Optional[int] = None,
-                         self_count: Optional[bool] = None, split: bool = False, slots: bool = False) -> Banded:
+                         self_count: Optional[bool] = None, split: bool = False, slots: bool = False,
+                         triples: bool = False) -> Banded:
         """Banded transpose of Phi.  counted_ws: workspace whose bucket counts ``walk_phi`` filled.
         staged: two-pass binned fill (default when band_width % 64 == 0) or the atomic fill.
         self_count: the staged fill without a plan (grf_transpose_banded_self; default unless
@@ -562,7 +566,10 @@ class GRFEngine:
         slots: (self-count transpose) where the buckets are sparse enough for packed pairs and the bands
         wider than 4096 (8-wave Gram tiles), the GRF_REC_SLOT layout instead: each bucket's header and
         first two pairs in one 32-byte slot, so the Gram reads a small bucket with one line (the column
-        blocks over power-law graphs, C5).  Not for the hub-column split (which edits descriptors)."""
+        blocks over power-law graphs, C5).  Not for the hub-column split (which edits descriptors).
+        triples: (self-count transpose, band_width <= 4096, line buckets) 16-byte record triples instead of
+        12-byte pairs: three entries per gathered stream position of the Gram (``Banded.rec_kind``); with
+        split, slots, a wider band or the planned / atomic fills a ValueError (GRF_EINVAL), nothing launched."""
         n_rows, n_cols = phi.n_rows, phi.n_cols
         nb = -(-n_rows // band_width)
         nbk = nb * n_cols
@@ -573,13 +580,18 @@ class GRFEngine:
             staged = band_width % 64 == 0 and os.environ.get("GRF_TRANSPOSE_STAGED", "1") != "0"
         if self_count is None:
             self_count = SELF_COUNT_TRANSPOSE and counted_ws is None and staged
+        if triples and not self_count:
+            raise ValueError("transpose_banded: record triples come from the self-counting transpose only "
+                             "(not the planned or atomic fills)")
         if self_count:
             if counted_ws is not None or not staged:
                 raise ValueError("self_count: the staged transpose counts its own buckets (no counted_ws)")
-            if slots and not split and rec_unit is None and band_width > 4096:
+            if triples:  # (line buckets; the library refuses split, slots and bands wider than 4096)
+                rec_unit = C.REC_SLOT if slots else C.REC_LINE if rec_unit is None else rec_unit
+            elif slots and not split and rec_unit is None and band_width > 4096:
                 u0 = _phi_rec_unit(phi, nnz_bound, band_width)
                 rec_unit = C.REC_SLOT if u0 == C.REC_PACKED else u0
-            return self._transpose_self(phi, band_width, nnz_bound, rec_unit, t_desc, t_max, t_shift, split)
+            return self._transpose_self(phi, band_width, nnz_bound, rec_unit, t_desc, t_max, t_shift, split, triples)
         ws = counted_ws if counted_ws is not None else self._ws(self.lib.grf_transpose_workspace_bytes(nbk))
         if rec_unit is None:
             rec_unit = _phi_rec_unit(phi, nnz_bound, band_width)
@@ -623,7 +635,7 @@ class GRFEngine:
         return Banded(t_desc, t_rec, t_max, t_shift, band_width, n_rows, n_cols, u)
 
     def _transpose_self(self, phi: DeviceCSR, band_width: int, nnz_bound: Optional[int], rec_unit: Optional[int],
-                        t_desc, t_max, t_shift, split: bool = False) -> Banded:
+                        t_desc, t_max, t_shift, split: bool = False, triples: bool = False) -> Banded:
         """The plan-free staged transpose (grf_transpose_banded_self): buckets counted by the placing
         workgroups themselves, no counts from the walk and no scan over every bucket."""
         n_rows, n_cols = phi.n_rows, phi.n_cols
@@ -633,11 +645,17 @@ class GRFEngine:
         u = int(rec_unit)
         # the Gram addresses a band's records with 32-bit byte offsets: bound one band's slabs
         row_cap = min(n_cols, max(1, -(-nnz // max(n_rows, 1))))
-        band_units = self.lib.grf_transpose_self_units_bound(min(band_width, n_rows), n_cols, band_width, u,
-                                                             min(nnz, band_width * row_cap))
+        kind = C.REC_TRIPLES if triples else C.REC_PAIRS
+
+        def units_bound(rows: int, entries: int) -> int:
+            if triples:
+                return self.lib.grf_transpose_self_triples_lines_bound(rows, n_cols, band_width, entries)
+            return self.lib.grf_transpose_self_units_bound(rows, n_cols, band_width, u, entries)
+
+        band_units = units_bound(min(band_width, n_rows), min(nnz, band_width * row_cap))
         if n_rows and band_units * u >= 2 ** 31:
             raise NotImplementedError("a transpose band holds >= 2 GiB of records; use a smaller band_width")
-        units = self.lib.grf_transpose_self_units_bound(n_rows, n_cols, band_width, u, nnz)
+        units = units_bound(n_rows, nnz)
         if u == C.REC_SLOT and units * u >= 2 ** 30:
             # (slot offsets are counted from the first slot of all bands: fall back to packed pairs)
             return self._transpose_self(phi, band_width, nnz_bound, C.REC_PACKED, t_desc, t_max, t_shift, split)
@@ -646,11 +664,12 @@ class GRFEngine:
         sg = self._ws(self.lib.grf_transpose_staging_bytes(n_rows, n_cols, band_width, nnz))
         nbk = -(-n_rows // band_width) * n_cols
         t_split = self._empty(8 * nbk, torch.int16) if split and band_width <= 8192 else None
-        C.check(self.lib.grf_transpose_banded_self(n_rows, n_cols, band_width, u, _p(phi.ptr), _p(phi.idx),
-                                                   _p(phi.val32), _p(t_desc), _p(t_split), _p(t_rec), t_rec.numel(),
-                                                   _p(t_max), _p(t_shift), _p(ws), ws.numel(), nnz, _p(sg),
-                                                   sg.numel(), self.stream), "grf_transpose_banded_self")
-        return Banded(t_desc, t_rec, t_max, t_shift, band_width, n_rows, n_cols, u, t_split)
+        C.check(self.lib.grf_transpose_banded_self_rec(kind, n_rows, n_cols, band_width, u, _p(phi.ptr), _p(phi.idx),
+                                                       _p(phi.val32), _p(t_desc), _p(t_split), _p(t_rec),
+                                                       t_rec.numel(), _p(t_max), _p(t_shift), _p(ws), ws.numel(), nnz,
+                                                       _p(sg), sg.numel(), self.stream),
+                "grf_transpose_banded_self_rec")
+        return Banded(t_desc, t_rec, t_max, t_shift, band_width, n_rows, n_cols, u, t_split, kind)
 
     # ----------------------------------------------------------------- Gram
     @staticmethod
@@ -665,11 +684,10 @@ class GRFEngine:
         ldk = self.leading_dim(n)
         if out is None:
             out = torch.empty((row_end - row_begin, ldk), dtype=torch.float32, device=self.device)
-        C.check(self.lib.grf_gram_sparse(n, row_begin, row_end, _p(phi.ptr), _p(phi.idx), _p(phi.val32),
-                                         tr.band_width, tr.rec_unit, _p(tr.t_desc), _p(tr.t_rec),
-                                         _p(tr.t_rowshift), _p(out),
-                                         out.stride(0), _p(self._gram_ws), self._gram_ws.numel(), self.stream),
-                "grf_gram_sparse")
+        C.check(self.lib.grf_gram_sparse_rec(tr.rec_kind, n, row_begin, row_end, _p(phi.ptr), _p(phi.idx),
+                                             _p(phi.val32), tr.band_width, tr.rec_unit, _p(tr.t_desc), _p(tr.t_rec),
+                                             _p(tr.t_rowshift), _p(out), out.stride(0), self.stream),
+                "grf_gram_sparse_rec")
         return out[:, :n]
 
     def phi_row_shifts(self, phi: DeviceCSR) -> torch.Tensor:
@@ -706,6 +724,7 @@ class GRFEngine:
         n = phi.n_rows
         row_end = n if row_end is None else row_end
         t_rows = tr_b.n_rows
+        self._pairs_only(tr_b, "gram_sparse_cols")
         if out is None:
             out = torch.empty((row_end - row_begin, self.leading_dim(max(t_rows, 1))), dtype=torch.float32,
                               device=self.device)
@@ -726,12 +745,18 @@ class GRFEngine:
                 "grf_gram_sparse_cols")
         return out[:, :t_rows]
 
+    @staticmethod
+    def _pairs_only(tr: Banded, who: str) -> None:
+        if tr.rec_kind != C.REC_PAIRS:
+            raise ValueError(f"{who}: record triples are read by the whole-K and row Gram only")
+
     def gram_sparse_kslice(self, phi: DeviceCSR, tr: Banded, k_begin: int, k_end: int, row_begin: int = 0,
                            row_end: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Partial K[row_begin:row_end, :] over the inner-dimension slice [k_begin, k_end) (float32)."""
         n = tr.n_rows
         row_end = n if row_end is None else row_end
         ldk = self.leading_dim(n)
+        self._pairs_only(tr, "gram_sparse_kslice")
         if out is None:
             out = torch.empty((row_end - row_begin, ldk), dtype=torch.float32, device=self.device)
         C.check(self.lib.grf_gram_sparse_kslice(n, row_begin, row_end, k_begin, k_end, _p(phi.ptr), _p(phi.idx),
@@ -750,7 +775,7 @@ class GRFEngine:
         if out is None:
             out = torch.empty((n, ldk), dtype=torch.float32, device=self.device)
         cuts = self.row_cuts(phi, tr, skewed)
-        if cuts is not None:  # (the waves' pair-balanced shares: same bits)
+        if cuts is not None or tr.rec_kind != C.REC_PAIRS:  # (the waves' pair-balanced shares: same bits)
             self._gram_upper_cuts(phi, tr, out, cuts, (0, 1, 1), False)
             self.gram_mirror(out, n)
             return out[:, :n]
@@ -763,7 +788,8 @@ class GRFEngine:
 
     def row_cuts(self, phi: DeviceCSR, tr: Banded, skewed: bool = False) -> Optional[torch.Tensor]:
         """8 cuts per row of Phi splitting its nonzeros into shares of about equal record pairs (weights:
-        every column's pairs over all bands of ``tr``), for the whole-K Gram's waves; None when the
+        every column's pairs -- or triples: the descriptors' counts -- over all bands of ``tr``), for the whole-K
+        Gram's waves; None when the
         policy says no (GRF_GRAM_CUTS: auto = when ``skewed``, ``column_stats``) or the buckets are slots.
         Measured: Facebook 2.86-2.91 -> 2.75-2.79 ms per K; C4 (not skewed) would pay 0.5 ms for the
         cuts and gain nothing (profiles/r03_gram_balance_ab.txt)."""
@@ -777,13 +803,15 @@ class GRFEngine:
                                            _p(col_w), _p(cuts), self.stream), "grf_gram_row_cuts")
         return cuts
 
-    def _gram_upper_cuts(self, phi: DeviceCSR, tr: Banded, out: torch.Tensor, cuts: torch.Tensor, parts,
+    def _gram_upper_cuts(self, phi: DeviceCSR, tr: Banded, out: torch.Tensor, cuts: Optional[torch.Tensor], parts,
                          add_k: bool) -> None:
-        C.check(self.lib.grf_gram_sparse_upper_ex(tr.n_rows, _p(phi.ptr), _p(phi.idx), _p(phi.val32), tr.band_width,
-                                                  tr.rec_unit, _p(tr.t_desc), _p(tr.t_rec), _p(tr.t_split),
-                                                  _p(tr.t_rowshift), _p(cuts), _p(out), out.stride(0), int(parts[0]),
-                                                  int(parts[1]), int(parts[2]), int(add_k), self.stream),
-                "grf_gram_sparse_upper_ex")
+        """The upper tiles of either record kind, with row cuts or (None) without."""
+        C.check(self.lib.grf_gram_sparse_upper_rec(tr.rec_kind, tr.n_rows, _p(phi.ptr), _p(phi.idx), _p(phi.val32),
+                                                   tr.band_width, tr.rec_unit, _p(tr.t_desc), _p(tr.t_rec),
+                                                   _p(tr.t_split), _p(tr.t_rowshift), _p(cuts), _p(out), out.stride(0),
+                                                   int(parts[0]), int(parts[1]), int(parts[2]), int(add_k),
+                                                   self.stream),
+                "grf_gram_sparse_upper_rec")
 
     def gram_sparse_upper(self, phi: DeviceCSR, tr: Banded, out: torch.Tensor, parts=(0, 1, 1),
                           cuts: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -791,7 +819,7 @@ class GRFEngine:
         parts = (begin, end, n): only those parts of the band-major tile sequence cut into n.
         cuts: ``row_cuts(phi, tr)`` (the waves' pair-balanced shares; same bits)."""
         n = tr.n_rows
-        if cuts is not None:
+        if cuts is not None or tr.rec_kind != C.REC_PAIRS:
             self._gram_upper_cuts(phi, tr, out, cuts, parts, False)
             return out[:, :n]
         C.check(self.lib.grf_gram_sparse_upper(n, _p(phi.ptr), _p(phi.idx), _p(phi.val32), tr.band_width,
@@ -859,7 +887,7 @@ class GRFEngine:
         upper = self.lib.grf_gram_dense_split_upper if self.dense_precision == "split" else self.lib.grf_gram_dense_upper
         C.check(upper(n, h, _p(P), P.stride(0), _p(out), out.stride(0), self.stream), "grf_gram_dense_upper")
         cuts = self.row_cuts(phi, tr, skewed)  # (after the hub drop: the weights of the columns left)
-        if cuts is not None:
+        if cuts is not None or tr.rec_kind != C.REC_PAIRS:
             self._gram_upper_cuts(phi, tr, out, cuts, (0, 1, 1), True)
         else:
             C.check(self.lib.grf_gram_sparse_upper_add(n, _p(phi.ptr), _p(phi.idx), _p(phi.val32), tr.band_width,

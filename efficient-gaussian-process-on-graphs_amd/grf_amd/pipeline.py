@@ -26,7 +26,7 @@ import torch
 
 from . import _lib as C
 from .engine import (DEFAULT_BAND_WIDTH, ROWS_BAND_WIDTH, SELF_COUNT_TRANSPOSE, DeviceCSR, GRFEngine, PaddedRows,
-                     cols_band_width)
+                     _phi_rec_unit, cols_band_width)
 
 # column blocks with sparse buckets take the GRF_REC_SLOT transpose (GRF_REC_SLOTS=0: packed pairs, A/B)
 SLOTS_DEFAULT = os.environ.get("GRF_REC_SLOTS", "1") == "1"
@@ -41,6 +41,19 @@ PADDED_PHI = os.environ.get("GRF_PADDED_PHI", "1") == "1"
 # not at the mirror (Enron 8.66-8.68 -> 8.13-8.23 ms per K, profiles/r03_hub_early_front_ab.txt;
 # GRF_HUB_EARLY_FRONT=0: at the mirror)
 HUB_EARLY_FRONT = os.environ.get("GRF_HUB_EARLY_FRONT", "1") == "1"
+# whole symmetric K, bands of at most 4096 rows, Phi's column counts not skewed (C4's Erdos-Renyi Phi): the transpose's
+# line buckets hold 16-byte record triples, three entries per gathered stream position of the Gram tiles (C4 22.81 ->
+# 21.84 ms per K).  Skewed Phi (``StepPlan.skewed``, the policy of the row cuts; Facebook, Enron) keeps 12-byte pairs:
+# measured 1.94 -> 2.81 and 7.28 -> 8.67 ms per K with triples (profiles/AB_LOG.md "Record triples").
+# GRF_REC_TRIPLES=0: pairs everywhere, 1: triples on skewed Phi too (A/B; read per front)
+TRIPLES_MAX_BAND = 4096
+
+
+def rec_triples(pl: "StepPlan") -> bool:
+    flag = os.environ.get("GRF_REC_TRIPLES", "auto")
+    if pl.mode != "sym" or pl.band_width > TRIPLES_MAX_BAND or flag == "0":
+        return False
+    return flag == "1" or not (pl.skewed or pl.hubs > 0)
 
 
 @dataclass
@@ -232,8 +245,12 @@ def front_transpose(eng: GRFEngine, pl: StepPlan, fr: Front) -> Front:
     """The second part: the banded transpose of the (gathered) Phi, sized from bounds (n x the padded
     row capacity): no host round trip.  (No sub-band split: the symmetric diagonal tiles' skip saves
     records, not lines, and measured no faster: profiles/r03_split_ab.txt.)"""
-    fr.tr = eng.transpose_banded(fr.phi, pl.band_width, counted_ws=getattr(fr, "tws", None),
-                                 nnz_bound=pl.n * pl.rows_cap)
+    tws = getattr(fr, "tws", None)
+    # (record triples come from the self-counting transpose: not when the walk counted the buckets ...
+    # ... and as line buckets, so only where the pairs would be line buckets too)
+    nnz_bound = pl.n * pl.rows_cap
+    triples = tws is None and rec_triples(pl) and _phi_rec_unit(fr.phi, nnz_bound, pl.band_width) == C.REC_LINE
+    fr.tr = eng.transpose_banded(fr.phi, pl.band_width, counted_ws=tws, nnz_bound=nnz_bound, triples=triples)
     # the whole-K tiles' pair-balanced wave shares (policy: engine.ROW_CUTS; the hub split makes its own
     # after dropping the hub columns)
     fr.cuts = eng.row_cuts(fr.phi, fr.tr, pl.skewed) if pl.mode == "sym" and pl.hubs == 0 else None

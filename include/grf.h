@@ -71,7 +71,8 @@ enum grf_norm {
 /* The ABI revision of this header: grf_version() returns it, and a binding must refuse a library whose
  * revision differs (argument lists, or -- ABI 7 -- the GRF_RNG_PHILOX stream, change between revisions;
  * ABI 8 added grf_phi_row_shifts_padded and grf_gram_sparse_cols_padded; ABI 9 the marginal likelihood's
- * grf_cg_gram_solve_lanczos_f64 and grf_steps_frob_f64; grf_spgemm_* came later, purely additive). */
+ * grf_cg_gram_solve_lanczos_f64 and grf_steps_frob_f64; grf_spgemm_* and the record kinds' *_rec entries came
+ * later, purely additive: no argument list of revision 9 changed, so the revision stays). */
 #define GRF_ABI_VERSION 9
 
 const char *grf_last_error(void);
@@ -278,6 +279,24 @@ size_t grf_transpose_self_workspace_bytes(int64_t n_rows, int64_t n_cols, int64_
 int64_t grf_transpose_self_units_bound(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
                                        int64_t nnz);
 
+/* Record kinds (additive to ABI 9).  GRF_REC_PAIRS: the 12-byte pairs {u16 8 * row0 | u16 8 * row1 << 16, f32 v0, f32 v1} of
+ * every entry point above.  GRF_REC_TRIPLES: 16-byte triples {u32 cols, f32 v0, f32 v1, f32 v2}, 8 per 128-byte
+ * line, cols = c0 | o1 << 12 | o2 << 22 with c0 the first entry's row in the band and o1 / o2 the other entries'
+ * rows as offsets from c0 & ~511 (the start of c0's aligned 512-row block of the band).  A bucket's entries are
+ * laid out by block and cut greedily: a triple whose first entry is in block e takes the following entries while
+ * they lie in block e or e + 1; unused places are padding (row c0, +0.0).  Triples exist as line buckets only:
+ * rec_unit = GRF_REC_LINE, band_width <= 4096, no t_split (NULL) -- anything else is GRF_EINVAL, nothing launched
+ * -- and only from grf_transpose_banded_self_rec, which is grf_transpose_banded_self for the given kind;
+ * t_desc holds {first line, triples} per bucket and t_rec >= grf_transpose_self_triples_lines_bound(...) * 128
+ * bytes.  The Gram entries below read either kind; K's bits do not depend on it (integer sums, padding adds 0). */
+enum grf_rec_kind { GRF_REC_PAIRS = 0, GRF_REC_TRIPLES = 1 };
+int32_t grf_transpose_banded_self_rec(int32_t rec_kind, int64_t n_rows, int64_t n_cols, int64_t band_width,
+                                      int32_t rec_unit, const int64_t *ptr, const int32_t *idx, const float *val,
+                                      uint32_t *t_desc, void *t_split, void *t_rec, int64_t t_rec_bytes,
+                                      float *t_maxabs, int32_t *t_rowshift, void *workspace, size_t workspace_bytes,
+                                      int64_t nnz, void *staging, size_t staging_bytes, grf_stream_t stream);
+int64_t grf_transpose_self_triples_lines_bound(int64_t n_rows, int64_t n_cols, int64_t band_width, int64_t nnz);
+
 /* ---------------------------------------------------------------------- Gram
  * Replaces `Phi @ Phi.T` of fast_grf_kernel_general.py:55 (sparse) and :39 (dense).
  * Sparse path: K[r, :] for rows r in [row_begin, row_end) of Phi (compact CSR,
@@ -349,6 +368,20 @@ int32_t grf_gram_sparse_upper_ex(int64_t n_total, const int64_t *ptr, const int3
                                  const void *t_split, const int32_t *t_rowshift, const int32_t *row_cuts, float *K,
                                  int64_t ldk, int32_t part_begin, int32_t part_end, int32_t n_parts, int32_t add_k,
                                  grf_stream_t stream);
+
+/* grf_gram_sparse and grf_gram_sparse_upper_ex for a transpose of the given record kind (additive to ABI 9; GRF_REC_PAIRS:
+ * exactly those calls).  GRF_REC_TRIPLES: line buckets of grf_transpose_banded_self_rec, band_width <= 4096,
+ * t_split NULL, else GRF_EINVAL.  grf_gram_row_cuts and grf_transpose_drop_columns read and edit the
+ * descriptors' counts alone and serve both kinds. */
+int32_t grf_gram_sparse_rec(int32_t rec_kind, int64_t n_total, int64_t row_begin, int64_t row_end, const int64_t *ptr,
+                            const int32_t *idx, const float *val, int64_t band_width, int32_t rec_unit,
+                            const uint32_t *t_desc, const void *t_rec, const int32_t *t_rowshift, float *K, int64_t ldk,
+                            grf_stream_t stream);
+int32_t grf_gram_sparse_upper_rec(int32_t rec_kind, int64_t n_total, const int64_t *ptr, const int32_t *idx,
+                                  const float *val, int64_t band_width, int32_t rec_unit, const uint32_t *t_desc,
+                                  const void *t_rec, const void *t_split, const int32_t *t_rowshift,
+                                  const int32_t *row_cuts, float *K, int64_t ldk, int32_t part_begin, int32_t part_end,
+                                  int32_t n_parts, int32_t add_k, grf_stream_t stream);
 
 /* Hub-column split (hub-heavy graphs: Enron, Facebook, power-law).  grf_hub_panel writes the entries
  * Phi[r, k] of the columns with hub_pos[k] >= 0 into the dense fp32 panel P[r, hub_pos[k]] (row-major,
