@@ -30,6 +30,9 @@ except ImportError:  # pragma: no cover - depends on the environment
     _Base = torch.nn.Module
 
 
+EVAL_CG_TOLERANCE = 1e-2  # gpytorch.settings.eval_cg_tolerance: the solves of a prediction
+
+
 def _noise_value(likelihood) -> float:
     noise = likelihood.noise if hasattr(likelihood, "noise") else likelihood
     return float(noise.item() if torch.is_tensor(noise) else noise)
@@ -103,3 +106,58 @@ class SparseGraphGP(_Base):
             eps1_batch, eps2_batch, tolerance=tolerance, max_iter=max_iter, dtype=cg_dtype,
             f=self.covar_module.modulator_vector if op is not None else None)
         return out.to(torch.float32)
+
+    def _moments(self, x_test, full_cov, tolerance, max_iter, add_noise):
+        dev = x_test.device
+        eng = get_engine(dev if dev.type == "cuda" else None)
+        op = self.covar_module._operator()
+        if op is not None and op.engine.device != eng.device:
+            raise ValueError("predict_f: the walk operator lives on another device than x_test")
+        phi = op if op is not None else self._phi_csr(eng.device)
+        info = {}
+        out = eng.posterior_moments(
+            phi, self.x_train.int().flatten().to(eng.device), x_test.int().flatten().to(eng.device), self.y_train,
+            _noise_value(self.likelihood), f=self.covar_module.modulator_vector if op is not None else None,
+            full_cov=full_cov, tolerance=EVAL_CG_TOLERANCE if tolerance is None else float(tolerance),
+            max_iter=max_iter, info=info, add_noise=add_noise)
+        self.last_cg_iterations = max(info["cg_iterations"] + [info["alpha_iterations"]])
+        return out
+
+    @torch.no_grad()
+    def predict_f(self, x_test, full_cov=False, tolerance=None, max_iter=1000):
+        """The exact posterior mean and variance of the latent function at ``x_test``: (mean, var), fp64
+        tensors of shape (n_test,), or with ``full_cov`` (mean, cov) with cov (n_test x n_test) -- what the
+        reference's dense baseline returns from ``model.predict_f`` (run_scaling_experiment.py:729) and its
+        sparse model can only estimate from pathwise samples (``predict(...).mean(0) / .std(0)``).
+
+        K is never formed: the test nodes go through batched CG solves of 256 columns on the walk's Phi or on
+        the WalkPolynomial operator, whichever the model was built on (``GRFEngine.posterior_moments``).
+        ``tolerance`` defaults to gpytorch's eval_cg_tolerance (1e-2), not the training default of 1.
+
+        Variances are returned as computed, never clamped.  What makes that safe is a property of CG: from a
+        zero start, b^T x_k increases monotonically to b^T K^-1 b, so a solve that stops early over-estimates
+        the variance and never under-estimates it, up to rounding.  In floating point that holds for b^T x_k
+        only while CG keeps its residual orthogonal to the Krylov space (b^T K^-1 b - b^T x_k =
+        ||x - x_k||^2_K + x_k^T r_k, and on the walk's ill-conditioned Phi the last term put a stopped solve
+        1e-4 of the prior below the truth), so the variance is formed from the energy form
+        x_k^T (2 b - K^ x_k) = b^T K^-1 b - ||x - x_k||^2_K, which is below b^T K^-1 b for any x_k at the cost of
+        one more operator product per chunk.
+        ``last_cg_iterations`` is the largest iteration count over the chunks' solves and the solve for the
+        mean."""
+        return self._moments(x_test, full_cov, tolerance, max_iter, False)
+
+    @torch.no_grad()
+    def predict_y(self, x_test, full_cov=False, tolerance=None, max_iter=1000):
+        """``predict_f`` for the noisy observation: the noise variance added to the variances, or to the
+        covariance's diagonal."""
+        return self._moments(x_test, full_cov, tolerance, max_iter, True)
+
+    @torch.no_grad()
+    def nlpd(self, x_test, y_test, tolerance=None, max_iter=1000):
+        """The negative log predictive density of ``y_test`` under ``predict_y``'s marginals, by the reference's
+        formula (wind_experiment.py:319-324): an fp64 scalar tensor."""
+        mean, var = self.predict_y(x_test, tolerance=tolerance, max_iter=max_iter)
+        y = y_test.to(mean.device, torch.float64).flatten()
+        std = var.sqrt()
+        z = (y - mean) / std
+        return (0.5 * torch.log(2.0 * torch.pi * std * std) + 0.5 * z * z).mean()

@@ -189,6 +189,11 @@ SIGNATURES = {
     "grf_expm_squarings": (_i32, [_dbl]),
     "grf_expm_sym_f64_workspace_bytes": (_sz, [_i64]),
     "grf_expm_sym_f64": (_i32, [_i64, _vp, _i64, _dbl, _dbl, _vp, _i64, _vp, _sz, _vp]),
+    # the exact posterior mean and variance: a chunk's right-hand sides E = Phi[x]^T with the prior variances, and
+    # the fused moment reduction over B and K^-1 B
+    "grf_posterior_rhs_f64": (_i32, [_i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "grf_posterior_reduce_workspace_bytes": (_sz, [_i64, _i32]),
+    "grf_posterior_reduce_f64": (_i32, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _dbl, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

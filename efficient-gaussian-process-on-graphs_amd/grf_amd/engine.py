@@ -1645,6 +1645,178 @@ class GRFEngine:
         out = f_test + self.spmm(phi, self.spmm(phi_t, V), te)                # + K_test_train v
         return out.t(), iters
 
+    # ------------------------------------- the exact posterior mean and variance (predict_f)
+    POSTERIOR_CHUNK = 256  # test nodes per batched solve: the solvers' column limit
+
+    def posterior_rhs(self, phi: DeviceCSR, nodes, E: Optional[torch.Tensor] = None,
+                      prior: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(E, prior) of <= 256 node indices (repeats allowed): E = Phi[nodes]^T as a dense (n_cols x S) fp64
+        block -- ``E`` may be a column window of a wider buffer, whose other columns stay untouched -- and
+        prior[c] = sum_k Phi[nodes[c], k]^2 = K[x_c, x_c] (grf_posterior_rhs_f64)."""
+        r = self._row_map(nodes)
+        S = r.numel()
+        if E is None:
+            E = torch.empty((phi.n_cols, S), dtype=torch.float64, device=self.device)
+        if prior is None:
+            prior = self._empty(S, torch.float64)
+        if E.dtype != torch.float64 or E.dim() != 2 or tuple(E.shape) != (phi.n_cols, S) or \
+                (S > 1 and E.stride(1) != 1) or prior.dtype != torch.float64 or prior.numel() != S \
+                or not prior.is_contiguous():
+            raise ValueError("posterior_rhs: E must be a float64 (n_cols x S) row-major block and prior hold S values")
+        C.check(self.lib.grf_posterior_rhs_f64(phi.n_rows, _p(phi.ptr), _p(phi.idx), _p(phi.val32), phi.n_cols, _p(r),
+                                               S, _p(E), self._pitch(E), _p(prior), self.stream),
+                "grf_posterior_rhs_f64")
+        return E, prior
+
+    def posterior_reduce(self, B: torch.Tensor, X: torch.Tensor, prior: torch.Tensor,
+                         alpha: Optional[torch.Tensor] = None, add_noise: float = 0.0,
+                         var: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None):
+        """var[c] = prior[c] - sum_r B[r,c] X[r,c] (+ add_noise) and, with ``alpha`` (n,), mean[c] =
+        sum_r B[r,c] alpha[r], in one deterministic pass over the (n x S) fp64 blocks B and X, S <= 256
+        (grf_posterior_reduce_f64).  Returns (var, mean); mean is None without alpha."""
+        if B.dim() != 2 or X.shape != B.shape:
+            raise ValueError("posterior_reduce: B and X must be (n x S) blocks of one shape")
+        n, S = int(B.shape[0]), int(B.shape[1])
+        self._check_block(B, n, "posterior_reduce: B")
+        self._check_block(X, n, "posterior_reduce: X")
+        if prior.dtype != torch.float64 or prior.numel() != S or not prior.is_contiguous():
+            raise ValueError("posterior_reduce: prior must hold one float64 per column")
+        if alpha is not None:
+            alpha = alpha.to(self.device, torch.float64).flatten().contiguous()
+            if alpha.numel() != n:
+                raise ValueError("posterior_reduce: alpha must hold one value per row")
+            if mean is None:
+                mean = self._empty(S, torch.float64)
+        if var is None:
+            var = self._empty(S, torch.float64)
+        ws = self._ws(self.lib.grf_posterior_reduce_workspace_bytes(n, S))
+        C.check(self.lib.grf_posterior_reduce_f64(n, S, _p(B), self._pitch(B), _p(X), self._pitch(X), _p(alpha),
+                                                  _p(prior), float(add_noise), _p(var),
+                                                  _p(mean) if alpha is not None else None, _p(ws), ws.numel(),
+                                                  self.stream), "grf_posterior_reduce_f64")
+        return var, (mean if alpha is not None else None)
+
+    def posterior_moments(self, phi, train_idx, test_idx, y_train: torch.Tensor, noise: float, *, f=None,
+                          full_cov: bool = False, tolerance: float = 1e-2, max_iter: int = 1000,
+                          info: Optional[dict] = None, add_noise: bool = False):
+        """The exact posterior mean and variance of the GP at ``test_idx`` (what the reference's dense baseline
+        calls predict_f, run_scaling_experiment.py:729), K never formed: with K^ = K[T,T] + noise I,
+        alpha = K^-1 y and b_c = K[T, x_c],
+            mean_c = b_c^T alpha,   var_c = K[x_c, x_c] - b_c^T K^-1 b_c,   cov = K[x,x] - B^T K^-1 B.
+        Returns (mean, var), fp64 device tensors of shape (n*,), or with ``full_cov`` (mean, cov), cov
+        (n* x n*) and exactly symmetric.  ``add_noise`` adds ``noise`` to the variances / the covariance's
+        diagonal (predict_y).  The test nodes (repeats and training nodes allowed) go in chunks of 256 columns,
+        one batched CG solve each; ``tolerance`` defaults to gpytorch's eval_cg_tolerance.  Variances are
+        returned as computed: from its zero start CG's b^T x_k rises monotonically to b^T K^-1 b, so a solve
+        stopped early over-estimates a variance and never under-estimates it, up to rounding.  So that this
+        also holds once CG has lost orthogonality, the quadratic form is taken as x^T (2 b - K^ x) =
+        b^T K^-1 b - ||x - x_k||^2_K (one more operator product per chunk); the mean is B^T alpha, and with
+        ``full_cov`` the off-diagonal entries are K[x,x] - B^T X symmetrised, the diagonal the variances.
+
+        phi: Phi as a DeviceCSR (rhs -> spmm -> cg_solve -> reduce per chunk), or a WalkPolynomial with its
+        modulator ``f`` (poly_kernel_block / poly_kernel_diag / cg_solve_poly, then the same reduce kernel).
+        ``info`` receives ``cg_iterations`` (a list, one count per chunk) and ``alpha_iterations``."""
+        poly = isinstance(phi, WalkPolynomial)
+        if poly and f is None:
+            raise ValueError("posterior_moments: a WalkPolynomial needs its modulator f")
+        tr, te = self._row_map(train_idx), self._row_map(test_idx)
+        n, ns = tr.numel(), te.numel()
+        y = y_train.detach().to(self.device, torch.float64).flatten()
+        if y.numel() != n:
+            raise ValueError("posterior_moments: y_train must hold one value per training node")
+        n_nodes = phi.shape[0] if poly else phi.n_cols
+        chunk = self.POSTERIOR_CHUNK
+        if full_cov:  # B for every test node, its transpose for the product, the result and its symmetrisation
+            self._dense_memory_guard("posterior_moments (full_cov)", max(n, ns),
+                                     2 * n * ns * 8 + 2 * ns * ns * 8 + (0 if poly else n_nodes * min(chunk, ns) * 8))
+        mean = torch.zeros(ns, dtype=torch.float64, device=self.device)
+        var = torch.empty(ns, dtype=torch.float64, device=self.device)
+        iters, alpha_iters = [], 0
+        if info is not None:
+            info["cg_iterations"], info["alpha_iterations"] = iters, 0
+        if ns == 0:
+            return mean, (torch.empty((0, 0), dtype=torch.float64, device=self.device) if full_cov else var)
+        phi_t, alpha = None, None
+        if n:
+            if poly:
+                alpha, alpha_iters = self.cg_solve_poly(phi, f, y[:, None].contiguous(), noise, tr, tolerance, max_iter)
+            else:
+                phi_t = self.csr_transpose(phi, tr)
+                alpha, alpha_iters = self.cg_solve(phi, y[:, None].contiguous(), noise, tr, phi_t, tolerance, max_iter)
+            alpha = alpha.flatten()
+        if info is not None:
+            info["alpha_iterations"] = alpha_iters
+        width = min(chunk, ns)
+        prior = torch.empty(ns, dtype=torch.float64, device=self.device)
+        E_buf = None if poly else torch.empty((n_nodes, width), dtype=torch.float64, device=self.device)
+        B_all = torch.empty((n, ns if full_cov else width), dtype=torch.float64, device=self.device)
+        cov = torch.empty((ns, ns), dtype=torch.float64, device=self.device) if full_cov else None
+        extra = float(noise) if add_noise else 0.0
+        scratch = torch.empty(width, dtype=torch.float64, device=self.device)
+
+        def rhs(c0, c1):
+            """B[:, c0:c1] = K[T, chunk] (a window of B_all), prior[c0:c1], and cov[:, c0:c1] = K[x, chunk]."""
+            S = c1 - c0
+            nodes = te[c0:c1]
+            Bv = B_all[:, c0:c1] if full_cov else B_all[:, :S]
+            if poly:
+                if n:
+                    Bv.copy_(self.poly_kernel_block(phi, f, x1=tr, x2=nodes))
+                prior[c0:c1] = self.poly_kernel_diag(phi, f, x=nodes)
+                if full_cov:
+                    cov[:, c0:c1] = self.poly_kernel_block(phi, f, x1=te, x2=nodes)
+                return Bv
+            E = E_buf[:, :S]
+            self.posterior_rhs(phi, nodes, E, prior[c0:c1])
+            if n:
+                self.spmm(phi, E, tr, out=Bv)
+            if full_cov:
+                self.spmm(phi, E, te, out=cov[:, c0:c1])
+            return Bv
+
+        def solve(Bv, c0, c1):
+            if n:
+                if poly:
+                    X, it = self.cg_solve_poly(phi, f, Bv, noise, tr, tolerance, max_iter)
+                else:
+                    X, it = self.cg_solve(phi, Bv, noise, tr, phi_t, tolerance, max_iter)
+            else:
+                X, it = Bv, 0
+            iters.append(it)
+            if not n:
+                self.posterior_reduce(Bv, X, prior[c0:c1], None, extra, var[c0:c1])
+                return X
+            # b^T x alone is below b^T K^-1 b only while CG keeps r_k orthogonal to its Krylov space; the
+            # energy form 2 b^T x - x^T K^ x = x^T (2 b - K^ x) is below it for any x, so the variance uses that
+            if poly:
+                KX = self.poly_gram_matvec(phi, f, X, rows=tr, cols=tr, noise=noise)
+            else:
+                KX = self.gram_matvec(phi, X, rows=tr, cols=tr, phi_t=phi_t, noise=noise)
+            KX.mul_(-1.0).add_(Bv, alpha=2.0)
+            self.posterior_reduce(KX, X, prior[c0:c1], None, extra, var[c0:c1])
+            self.posterior_reduce(Bv, X, prior[c0:c1], alpha, 0.0, scratch[:c1 - c0], mean[c0:c1])
+            return X
+
+        bounds = [(c0, min(c0 + chunk, ns)) for c0 in range(0, ns, chunk)]
+        if not full_cov:
+            for c0, c1 in bounds:
+                solve(rhs(c0, c1), c0, c1)
+            return mean, var
+        for c0, c1 in bounds:
+            rhs(c0, c1)
+        if n:
+            B_t = B_all.t().contiguous()                                       # (n* x n): read by rows in the product
+            for c0, c1 in bounds:
+                X = solve(B_all[:, c0:c1], c0, c1)
+                Cv = cov[:, c0:c1]
+                self.gemm_nt_f64(B_t, X.t().contiguous(), alpha=-1.0, Z=Cv, out=Cv)   # K[x, chunk] - B_all^T X
+        else:
+            for c0, c1 in bounds:
+                solve(B_all[:, c0:c1], c0, c1)
+        cov = (cov + cov.t()).mul_(0.5)
+        cov.diagonal().copy_(var)                                              # (the energy form, noise included)
+        return mean, cov
+
     # ------------------------------------------------------------- pipelines
     def kernel_matrix(self, A, modulator_vector: Sequence[float], walks_per_node: int, p_halt: float,
                       max_walk_length: int, *, rng: int = C.RNG_PHILOX, seed: int = 42, n_chunks: int = 1,

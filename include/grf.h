@@ -890,6 +890,49 @@ size_t grf_expm_sym_f64_workspace_bytes(int64_t n);
 int32_t grf_expm_sym_f64(int64_t n, const double *L, int64_t ldl, double beta, double rho, double *E, int64_t lde,
                          void *workspace, size_t workspace_bytes, grf_stream_t stream);
 
+/* ------------------------------------------- the exact posterior mean and variance (predict_f)
+ * For training nodes T (n of them), K^ = K[T,T] + s2 I, alpha = K^-1 y and test nodes x_c with b_c = K[T, x_c]:
+ *     mean_c = b_c^T alpha,    var_c = K[x_c, x_c] - b_c^T K^-1 b_c,    cov = K[x,x] - B^T K^-1 B,
+ * K never formed, the test nodes in chunks of <= 256 columns with one batched CG solve (grf_cg_gram_solve_f64 or
+ * grf_cg_poly_solve_f64) per chunk.  Replaces the reference's only route on the sparse model, the moments of 64
+ * pathwise samples (experiments/graph_bo/scripts/wind_experiment.py:396-398,
+ * experiments/sparse/scaling_exp/run_scaling_experiment.py:621: samples.mean(0) / samples.std(0), a standard
+ * deviation with ~9 % Monte-Carlo error), by what its dense baseline has (model.predict_f,
+ * run_scaling_experiment.py:729); the NLPD of wind_experiment.py:319-324 is evaluated on these moments.  Purely
+ * additive to ABI 9.
+ *
+ * grf_posterior_rhs_f64: the chunk's right-hand sides from Phi (the device CSR of grf_cg_gram_solve*: int64 row
+ * pointers, int32 columns, fp32 values; n_rows x n_cols) and n_nodes <= 256 node indices (device int32; repeats
+ * allowed; an index outside [0, n_rows) counts as an empty row):
+ *     E[k, c] = Phi[nodes[c], k]  (fp32 widened: exact), every other E[k, c], c < n_nodes, zero;
+ *     prior[c] = sum_k Phi[nodes[c], k]^2 = K[x_c, x_c].
+ * E: n_cols x n_nodes fp64 row-major, lde >= n_nodes; the columns [n_nodes, lde) of a row are never written.
+ * B = Phi[T] E is then one grf_spmm_csr_f64.  Order rule: the squares (exact in fp64) are added to +0.0 one by one
+ * in the row's stored order, without FMA.  n_nodes == 0 touches nothing.
+ *
+ * grf_posterior_reduce_f64: one pass over B and X = K^-1 B (n x n_rhs fp64 row-major, pitches ldb, ldx >= n_rhs):
+ *     q[c] = sum_r B[r,c] X[r,c],   var[c] = (prior[c] - q[c]) + add_noise  (never clamped),
+ *     mean[c] = sum_r B[r,c] alpha[r]   (alpha[n] and mean both NULL: no mean).
+ * (The engine calls it twice per chunk: with 2 B - K^ X in B's place for the variances -- x^T (2 b - K^ x) is below
+ * b^T K^-1 b for any x, b^T x only while CG keeps its orthogonality -- and with B and alpha for the mean.)
+ * Order rule (fp64, no floating-point atomics: two calls give the same bits, and a permutation of the columns
+ * permutes the results bit for bit): with P the power of two >= min(n_rhs, 64) a wave covers 64 / P rows at a
+ * time; the rows are cut into consecutive blocks whose length depends on (n, n_rhs) alone; within a block a lane
+ * adds its rows ascending by fma from +0.0, lanes of one column by an xor tree, the eight waves in order; one
+ * partial per (block, column); the last block (a ticket at the workspace's start, zero again afterwards) adds
+ * them in block order within G = 512 / (64 ceil(n_rhs / 64)) groups of consecutive blocks, then the groups in
+ * order.  Summation depth <= rows per lane + 6 + 7 + 256 blocks.
+ * n_rhs in [0, 256] (0 touches nothing); n == 0 writes var = prior + add_noise and mean = 0.  var and mean must
+ * overlap neither an input, the workspace nor each other.  Workspace: grf_posterior_reduce_workspace_bytes. */
+int32_t grf_posterior_rhs_f64(int64_t n_rows, const int64_t *ptr, const int32_t *idx, const float *val,
+                              int64_t n_cols, const int32_t *nodes, int32_t n_nodes, double *E, int64_t lde,
+                              double *prior, grf_stream_t stream);
+size_t grf_posterior_reduce_workspace_bytes(int64_t n, int32_t n_rhs);
+int32_t grf_posterior_reduce_f64(int64_t n, int32_t n_rhs, const double *B, int64_t ldb, const double *X,
+                                 int64_t ldx, const double *alpha, const double *prior, double add_noise,
+                                 double *var, double *mean, void *workspace, size_t workspace_bytes,
+                                 grf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
