@@ -25,6 +25,11 @@
 // gram_tile_out (the write-out).  On the host the entry points fill one GramArgs, checked by gram_check and run by
 // gram_tiles_launch (one loop over launches of at most 2^32 work-items).  GRF_GRAM_PIPE is the one environment
 // variable read here; the measured-and-decided choices (waves per tile, the split, the shares) are plain rules.
+// The tile order and its two locate forms live in grf_gram_tiles.h.  The symmetric whole-K launches of 4-wave tiles
+// without sub-band split, row cuts or hub add (the benchmarked C4 step, Enron; any part of such a launch) take the
+// plain instantiation gram_sparse_kernel<4, 2, false, kRec, true> = gram_plain_tile: (band, row) from 32-bit host
+// constants, loads before zeroing, none of the generic tile's switches.  Row, column-block, k-slice, slot, 8-wave,
+// split, row-cut and add launches -- and any launch past 31 bits -- take the generic tile with the 64-bit locate.
 //
 // Dense path: grf_gram_dense.hip (fp32 MFMA, 128 x 128 tiles on and above the diagonal).
 #include <stdio.h>
@@ -33,6 +38,7 @@
 #include <algorithm>
 
 #include "grf_block.h"
+#include "grf_gram_tiles.h"
 
 namespace grf {
 
@@ -278,15 +284,31 @@ __device__ __forceinline__ void slot_buckets(uint2 d, int32_t sb, int32_t ovf_ba
 }
 
 constexpr int kGramUnroll = 8;  // windows of gathers in flight per wave (4 and 16 measured slower: AB_LOG rounds 1..3)
+// ... of the plain whole-K tile (gram_plain_tile): without the generic tile's prologue and spills the order turns
+// round -- 3 and 4 measured fastest, 6, 7, 8, 12, 16 slower in that order (AB_LOG, "tile coordinates")
+constexpr int kPlainUnroll = 4;
+
+// the exact tail group of nw (1 .. N) windows
+template <int N, int kRec>
+__device__ __forceinline__ void gram_tail_group(const GramStream &gs, int nw, int32_t w0, int32_t c0, int32_t cend,
+                                                int lane) {
+    if constexpr (N > 1) {
+        if (nw < N) {
+            gram_tail_group<N - 1, kRec>(gs, nw, w0, c0, cend, lane);
+            return;
+        }
+    }
+    gram_windows<N, 1, kRec>(gs, w0, c0, cend, lane);
+}
 
 // One batch of a wave: lane l holds the buckets h * 64 + l (h < kV) -- cnt pairs from byte t0 of the band's
 // records, times av = Phi[row, k] -- already in registers.  The buckets are flattened into one stream of pairs
 // (a scan of the counts), the bucket of every stream position comes from a u8 id per position (bucket-start
 // markers propagated by a running maximum, in chunks of 256 / 512 / 1024 positions: the propagation's VALU scales
-// with the chunk), and the stream is gathered and added in groups of kGramUnroll windows of 64 pairs, the last
-// group with exactly the windows left (a full group would issue up to kGramUnroll - 1 all-masked windows of loads
+// with the chunk), and the stream is gathered and added in groups of kU windows of 64 pairs, the last
+// group with exactly the windows left (a full group would issue up to kU - 1 all-masked windows of loads
 // and LDS adds per batch).
-template <int kV, int kRec = kPairBytesG>
+template <int kV, int kRec = kPairBytesG, int kU = kGramUnroll>
 __device__ __forceinline__ void gram_stream_batch(const GramStream &gs, const int32_t *cnt, const int32_t *t0,
                                                   const float *av, int lane) {
     const GramWaveState &st = gs.st;
@@ -322,21 +344,9 @@ __device__ __forceinline__ void gram_stream_batch(const GramStream &gs, const in
                                : gram_propagate_ids<4>(st.bid, carry, lane);
         __builtin_amdgcn_wave_barrier();
         int32_t w0 = c0;
-        for (; w0 + 64 * kGramUnroll <= cend; w0 += 64 * kGramUnroll)
-            gram_windows<kGramUnroll, 0, kRec>(gs, w0, c0, cend, lane);
-        if (w0 < cend) {
-            static_assert(kGramUnroll == 8, "the tail switch lists 1 .. 8 windows");
-            switch ((cend - w0 + 63) >> 6) {
-                case 1: gram_windows<1, 1, kRec>(gs, w0, c0, cend, lane); break;
-                case 2: gram_windows<2, 1, kRec>(gs, w0, c0, cend, lane); break;
-                case 3: gram_windows<3, 1, kRec>(gs, w0, c0, cend, lane); break;
-                case 4: gram_windows<4, 1, kRec>(gs, w0, c0, cend, lane); break;
-                case 5: gram_windows<5, 1, kRec>(gs, w0, c0, cend, lane); break;
-                case 6: gram_windows<6, 1, kRec>(gs, w0, c0, cend, lane); break;
-                case 7: gram_windows<7, 1, kRec>(gs, w0, c0, cend, lane); break;
-                default: gram_windows<8, 1, kRec>(gs, w0, c0, cend, lane); break;
-            }
-        }
+        for (; w0 + 64 * kU <= cend; w0 += 64 * kU)
+            gram_windows<kU, 0, kRec>(gs, w0, c0, cend, lane);
+        if (w0 < cend) gram_tail_group<kU, kRec>(gs, (cend - w0 + 63) >> 6, w0, c0, cend, lane);
         __builtin_amdgcn_wave_barrier();
     }
 }
@@ -349,8 +359,8 @@ typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 // addk: K already holds the dense hub-column part of these entries, and the sum is rounded once and added to it.
 // kZero: every accumulator written out is zeroed for the workgroup's next tile (the persistent kernel, c_lo = 0).
 template <bool kZero>
-__device__ __forceinline__ void gram_tile_out(unsigned long long *acc, float *krow, bool vec, int64_t c_lo,
-                                              int64_t wlen, int sh, bool addk, int tid, int threads) {
+__device__ __forceinline__ void gram_tile_out(unsigned long long *acc, float *krow, bool vec, int32_t c_lo,
+                                              int32_t wlen, int sh, bool addk, int tid, int threads) {
 #if GRF_GRAM_PIPE_ABLATE == 2
     constexpr bool store = !kZero;  // (timing-only build of the persistent kernel without its K stores: wrong K)
 #else
@@ -358,11 +368,11 @@ __device__ __forceinline__ void gram_tile_out(unsigned long long *acc, float *kr
 #endif
     u64x2 *acc2 = reinterpret_cast<u64x2 *>(acc);
     const u64x2 z2 = {0ull, 0ull};
-    int64_t done = c_lo;
+    int32_t done = c_lo;  // (a tile has at most 8192 columns: 32-bit indices)
     if (vec) {
-        const int64_t n4 = wlen / 4;
+        const int32_t n4 = wlen / 4;
         f32x4 *k4 = reinterpret_cast<f32x4 *>(krow);
-        for (int64_t i = c_lo / 4 + tid; i < n4; i += threads) {
+        for (int32_t i = c_lo / 4 + tid; i < n4; i += threads) {
             const u64x2 a = acc2[2 * i], b = acc2[2 * i + 1];
             f32x4 o;
             o[0] = fx_to_float(a[0], sh);
@@ -378,7 +388,7 @@ __device__ __forceinline__ void gram_tile_out(unsigned long long *acc, float *kr
         }
         done = n4 * 4;
     }
-    for (int64_t i = done + tid; i < wlen; i += threads) {
+    for (int32_t i = done + tid; i < wlen; i += threads) {
         if (store) krow[i] = addk ? fx_to_float(acc[i], sh) + krow[i] : fx_to_float(acc[i], sh);
         if (kZero) acc[i] = 0ull;
     }
@@ -389,41 +399,6 @@ __device__ __forceinline__ void gram_tile_out(unsigned long long *acc, float *kr
 constexpr size_t gram_lds_bytes(int64_t W, int waves, int halves) {
     return (size_t)W * 8 + (size_t)waves * wave_state_bytes(halves);
 }
-
-// Tiles of one Gram call in band-major order: band J holds count(J) tiles, the local rows
-// 0 .. count(J)-1 (full mode: all rows; symmetric mode, whole K: the rows of bands <= J).
-struct GramTiles {
-    int64_t rows, W, nb;
-    bool sym;
-    int32_t k_begin, k_end;  // only the nonzeros Phi[i, k] with k in [k_begin, k_end) contribute
-    int64_t J_off = 0;       // the launch's bands are the global bands J_off .. J_off + nb - 1
-    int64_t t_rows = -1;     // rows of the transposed matrix (< 0: n_total, the square case)
-    bool add_k = false;      // write-out adds to K (which holds the dense hub-column part: grf_gram_sparse_upper_add)
-    __host__ __device__ int64_t count(int64_t J) const {
-        if (!sym) return rows;
-        const int64_t c = (J + 1) * W;
-        return c < rows ? c : rows;
-    }
-    // tiles before band J
-    __host__ __device__ int64_t before(int64_t J) const {
-        if (!sym) return J * rows;
-        const int64_t full = (rows + W - 1) / W - 1;  // bands J < full hold (J + 1) W rows
-        return J <= full ? W * J * (J + 1) / 2 : W * full * (full + 1) / 2 + (J - full) * rows;
-    }
-    __host__ __device__ int64_t total() const { return before(nb); }
-    // band and local row of tile t
-    __device__ void locate(int64_t t, int64_t &J, int64_t &r) const {
-        if (!sym) {
-            J = t / rows;
-        } else {
-            J = (int64_t)((sqrt(8.0 * (double)(t / W) + 1.0) - 1.0) * 0.5);
-            if (J > nb - 1) J = nb - 1;
-            while (J > 0 && before(J) > t) --J;
-            while (J < nb - 1 && before(J + 1) <= t) ++J;
-        }
-        r = t - before(J);
-    }
-};
 
 // One workgroup of kWaves waves = one tile K[row, j0 : j0 + W] (W = a band of the banded
 // transpose), accumulated in LDS in exact int64 fixed point with the per-row power-of-two
@@ -443,9 +418,86 @@ struct GramTiles {
 // and a small bucket costs one line (header and pairs) instead of a descriptor line and a record line.
 // kRec: the line buckets hold 12-byte pairs (kPairBytesG; also every packed and slot transpose) or 16-byte triples
 // (kTripleBytesG: one stream position per three entries, d.y counts triples).
-template <int kWaves, int kHalves, bool kSlot, int kRec>
+// (LDS writes and reads done, then the workgroup's barrier: global loads stay in flight across it)
+__device__ __forceinline__ void pipe_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// The plain whole-K tile (kPlain): the symmetric launch over Phi's own transpose with none of the switches of the
+// generic tile below -- line buckets, no sub-band split, no row cuts, every column, K written not added to, rows
+// from 0, equal contiguous wave shares -- and the tile order as 32-bit host constants (GramTiles32).  (band, row)
+// come from a few scalar operations; the row's bounds, shift and the band's first line are loaded, then the wave's
+// first nonzeros and their descriptors, the accumulators are zeroed under those loads, and the workgroup's barrier
+// stands just before the first batch's adds.  A row's nonzeros are indexed from its first one in 32 bits (a row
+// has at most n_total < 2^31 of them).  Same integer sums as the generic tile: identical bits.
+template <int kWaves, int kHalves, int kRec>
+__device__ __forceinline__ void gram_plain_tile(unsigned long long *acc, uint32_t n_total, const GramTiles32 &t32,
+                                                uint32_t t, const int64_t *__restrict__ ptr,
+                                                const int32_t *__restrict__ idx, const float *__restrict__ val,
+                                                const uint2 *__restrict__ t_desc,
+                                                const unsigned char *__restrict__ t_rec, int32_t unit,
+                                                const int32_t *__restrict__ rowshift, float *__restrict__ K,
+                                                int64_t ldk) {
+    static_assert(kWaves > 1, "the plain tile synchronises its waves with s_barrier");
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int kB = 64 * kHalves;  // nonzeros per wave batch
+    uint32_t J, r;
+    t32.locate(t, J, r);
+    J += t32.J_off;  // global band
+    const uint32_t W = t32.W, j0 = J * W;  // (j0 < n_total)
+    const int32_t wlen = (int32_t)((n_total - j0) < W ? (n_total - j0) : W);
+    const uint2 *bdesc = t_desc + (uint64_t)J * n_total;  // the band's descriptors
+    const int64_t e0 = ptr[r], e1 = ptr[r + 1];
+    const int sh = rowshift[r];
+    const int32_t line0 = (int32_t)bdesc[0].x;  // the band's first unit
+    const int32_t *ridx = idx + e0;
+    const float *rval = val + e0;
+    // wave w takes the w-th of kWaves equal contiguous shares of the row, in batches of kB
+    const int32_t nnz_row = (int32_t)(e1 - e0), share = (nnz_row + kWaves - 1) / kWaves;
+    const int32_t s0 = min(wave * share, nnz_row), s1 = min((wave + 1) * share, nnz_row);
+
+    int32_t k[kHalves];
+    float av[kHalves];
+    uint2 d[kHalves];
+    auto load_batch = [&](int32_t g) {
+        const int32_t gend = min(g + kB, s1);
+#pragma unroll
+        for (int h = 0; h < kHalves; ++h) {
+            const int32_t e = g + h * 64 + lane;
+            k[h] = e < gend ? ridx[e] : -1;
+            av[h] = e < gend ? rval[e] : 0.f;
+        }
+#pragma unroll
+        for (int h = 0; h < kHalves; ++h) d[h] = k[h] >= 0 ? bdesc[k[h]] : make_uint2((uint32_t)line0, 0u);
+    };
+    load_batch(s0);
+    u64x2 *acc2 = reinterpret_cast<u64x2 *>(acc);
+    const u64x2 z2 = {0ull, 0ull};
+    for (int32_t i = tid; i < (int32_t)(W / 2); i += 64 * kWaves) acc2[i] = z2;
+    const GramStream gs{gram_wave_state(acc, W, wave, kHalves),
+                        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(t_rec + (int64_t)line0 * unit),
+                                                          (short)0, 0x7fffffff, 0x00020000),
+                        reinterpret_cast<unsigned char *>(acc), ldexp(1.0, sh), 0};
+    pipe_barrier();
+    for (int32_t g = s0; g < s1;) {
+        int32_t cnt[kHalves], t0[kHalves];
+#pragma unroll
+        for (int h = 0; h < kHalves; ++h) {
+            t0[h] = ((int32_t)d[h].x - line0) * unit;  // first byte within the band
+            cnt[h] = (int32_t)d[h].y;                  // records (pairs or triples)
+        }
+        gram_stream_batch<kHalves, kRec, kPlainUnroll>(gs, cnt, t0, av, lane);
+        g += kB;
+        if (g < s1) load_batch(g);
+    }
+    __syncthreads();
+    gram_tile_out<false>(acc, K + (int64_t)r * ldk + j0, (ldk & 3) == 0 && (j0 & 3) == 0, 0, wlen, sh, false, tid,
+                         64 * kWaves);
+}
+
+// kPlain: the tile is gram_plain_tile (t32 and t_begin < 2^31 from the host: gram_tiles_launch says which launches
+// qualify); the arguments it does not name are never loaded.
+template <int kWaves, int kHalves, bool kSlot, int kRec, bool kPlain = false>
 __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
-    int64_t n_total, int64_t row_begin, GramTiles tl, int64_t t_begin, const int64_t *__restrict__ ptr,
+    int64_t n_total, int64_t row_begin, GramTiles tl, GramTiles32 t32, int64_t t_begin, const int64_t *__restrict__ ptr,
     const int32_t *__restrict__ idx, const float *__restrict__ val, const uint2 *__restrict__ t_desc,
     const unsigned char *__restrict__ t_rec, int32_t unit, const int32_t *__restrict__ rowshift,
     float *__restrict__ K, int64_t ldk, const uint16_t *__restrict__ t_split,
@@ -453,6 +505,12 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];  // [W]
     static_assert(!kSlot || kHalves == 1, "slot streams: 2 virtual buckets per nonzero, u8 ids <= 128");
     static_assert(!kSlot || kRec == kPairBytesG, "slots hold pairs");
+    if constexpr (kPlain) {
+        static_assert(!kSlot, "the plain tile reads line or packed buckets");
+        gram_plain_tile<kWaves, kHalves, kRec>(acc, (uint32_t)n_total, t32, (uint32_t)t_begin + blockIdx.x, ptr, idx, val,
+                                               t_desc, t_rec, unit, rowshift, K, ldk);
+        return;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t W = tl.W;
     constexpr int kB = 64 * kHalves;        // nonzeros per wave batch
@@ -479,7 +537,7 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
 
     u64x2 *acc2 = reinterpret_cast<u64x2 *>(acc);
     const u64x2 z2 = {0ull, 0ull};
-    for (int64_t i = tid; i < W / 2; i += 64 * kWaves) acc2[i] = z2;
+    for (int32_t i = tid; i < (int32_t)(W / 2); i += 64 * kWaves) acc2[i] = z2;
     if (kWaves > 1) __syncthreads();
     else __builtin_amdgcn_wave_barrier();
 
@@ -534,7 +592,7 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
     else __builtin_amdgcn_wave_barrier();
 
     // write the tile once, from the row's sub-band on
-    gram_tile_out<false>(acc, K + r * ldk + j0, (ldk & 3) == 0 && (j0 & 3) == 0, (int64_t)dsub * (W / kSub), wlen, sh,
+    gram_tile_out<false>(acc, K + r * ldk + j0, (ldk & 3) == 0 && (j0 & 3) == 0, dsub * (int32_t)(W / kSub), (int32_t)wlen, sh,
                          tl.add_k, tid, 64 * kWaves);
 }
 
@@ -550,8 +608,6 @@ __global__ __launch_bounds__(64 * kWaves) void gram_sparse_kernel(
 // integer sums: identical bits.  Measured and removed (profiles/r06_c5_gram_ab.txt, AB_LOG round 6): gather and
 // store waves split by role around double accumulators in one workgroup per CU; loader waves filling an LDS
 // ring with each tile's nonzeros and headers; a wave prefetching the nonzeros into L2.
-__device__ __forceinline__ void pipe_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 struct PipeNz {     // one tile's first batch of this wave's nonzeros (one per lane) and its bounds
     int32_t k;      // column (-1: none)
     float a;        // Phi[row, k]
@@ -689,7 +745,7 @@ __global__ __launch_bounds__(64 * kWv) void gram_slot_pipe_kernel(
         // tile i out (non-temporal) and its accumulator zeroed
         const int64_t r = row - row_begin, j0 = J * W;
         const int64_t wlen = (t_rows - j0) < W ? (t_rows - j0) : W;
-        gram_tile_out<true>(acc, K + r * ldk + j0, (ldk & 3) == 0 && (j0 & 3) == 0, 0, wlen, T0.sh, false, tid,
+        gram_tile_out<true>(acc, K + r * ldk + j0, (ldk & 3) == 0 && (j0 & 3) == 0, 0, (int32_t)wlen, T0.sh, false, tid,
                             64 * kWv);
         pipe_barrier();
         T0 = T1;
@@ -953,7 +1009,7 @@ static int32_t gram_tiles_launch(const GramArgs &a, const GramTiles &tl, int64_t
     // 76 KiB per CU: 16 waves per CU either way); measured best at both widths; slot buckets: 8 waves
     // (one batch of 64 nonzeros per wave: two stream buckets each).  8 windows of gathers in flight per wave
     // and an exact-size last window group (the round-1..3 sweeps of 4 / 16 windows and of masked tails:
-    // profiles/AB_LOG.md)
+    // profiles/AB_LOG.md); the plain tile below: kPlainUnroll windows
     const int waves = (slot || tl.W > 4096) ? 8 : 4;
     const size_t lds = gram_lds_bytes(tl.W, waves, (slot || waves == 4) ? 2 : 1);
     // Equal contiguous shares of a row's nonzeros per wave (1) or round-robin batches (0): measured
@@ -965,14 +1021,23 @@ static int32_t gram_tiles_launch(const GramArgs &a, const GramTiles &tl, int64_t
     const int64_t max_tiles = ((1ll << 32) - 1) / (64 * waves);
     for (int64_t t0 = t_first; t0 < t_last; t0 += max_tiles) {
         const int64_t nt = (t_last - t0) < max_tiles ? (t_last - t0) : max_tiles;
-#define GRF_GRAM_LAUNCH(WV, H, SLOT, REC)                                                                         \
-    gram_sparse_kernel<WV, H, SLOT, REC><<<(unsigned)nt, 64 * WV, lds, a.st>>>(                                   \
-        a.n_total, a.row_begin, tl, t0, a.ptr, a.idx, a.val, reinterpret_cast<const uint2 *>(a.t_desc), rec, a.unit, \
-        a.rowshift, a.K, a.ldk, split, ovf_base, balance, a.row_cuts)
-        if (slot) GRF_GRAM_LAUNCH(8, 1, true, kPairBytesG);
-        else if (waves == 8) GRF_GRAM_LAUNCH(8, 1, false, kPairBytesG);
-        else if (a.rec_kind == GRF_REC_TRIPLES) GRF_GRAM_LAUNCH(4, 2, false, kTripleBytesG);
-        else GRF_GRAM_LAUNCH(4, 2, false, kPairBytesG);
+        // The plain instantiation: the symmetric whole-K launch (or a part of one) of 4-wave tiles with no split, no
+        // row cuts, every column and no add -- grf_gram_sparse_sym / _upper / _upper_ex / _upper_rec without t_split
+        // and row_cuts -- whose tile indices, columns and rows fit 31 bits.  Everything else is the generic tile.
+        GramTiles32 t32{};
+        const bool plain = !slot && waves == 4 && tl.sym && tl.t_rows < 0 && a.row_begin == 0 && !split &&
+                           !a.row_cuts && !tl.add_k && tl.k_begin == 0 && tl.k_end == a.n_total &&
+                           tl.rows == a.n_total && gram_tiles32(tl, a.n_total, t0, t0 + nt, t32);
+#define GRF_GRAM_LAUNCH(WV, H, SLOT, REC, PLAIN)                                                                  \
+    gram_sparse_kernel<WV, H, SLOT, REC, PLAIN><<<(unsigned)nt, 64 * WV, lds, a.st>>>(                            \
+        a.n_total, a.row_begin, tl, t32, t0, a.ptr, a.idx, a.val, reinterpret_cast<const uint2 *>(a.t_desc), rec, \
+        a.unit, a.rowshift, a.K, a.ldk, split, ovf_base, balance, a.row_cuts)
+        if (slot) GRF_GRAM_LAUNCH(8, 1, true, kPairBytesG, false);
+        else if (waves == 8) GRF_GRAM_LAUNCH(8, 1, false, kPairBytesG, false);
+        else if (a.rec_kind == GRF_REC_TRIPLES && plain) GRF_GRAM_LAUNCH(4, 2, false, kTripleBytesG, true);
+        else if (a.rec_kind == GRF_REC_TRIPLES) GRF_GRAM_LAUNCH(4, 2, false, kTripleBytesG, false);
+        else if (plain) GRF_GRAM_LAUNCH(4, 2, false, kPairBytesG, true);
+        else GRF_GRAM_LAUNCH(4, 2, false, kPairBytesG, false);
 #undef GRF_GRAM_LAUNCH
         GRF_CHECK_LAUNCH("gram_sparse_kernel");
     }
