@@ -21,6 +21,8 @@
 //                               finalises) and the vector updates of linear_cg.
 // The recurrence (cg_solve_impl) takes its matvec as a functor: GramMatVec is the two SpMMs above, PolyMatVec
 // the two Horner chains of the walk polynomial (grf_poly.hip: K = S_T p(G) p(G)^T S_T^T, no Phi formed).
+// kPre = true is the same recurrence with linear_cg's preconditioner closure z = dinv . r for a diagonal (grf_pcg_*):
+// z is formed in the reductions and in cg_dir_kernel, never stored; gram_jacobi_kernel makes dinv = 1 / diag(K^).
 // All CG kernels read a device `done` flag first: once the stopping rule fires
 // the rest of the enqueued iterations are no-ops, so the host only polls the
 // flag and never serialises the stream per iteration.
@@ -310,6 +312,8 @@ struct CgState {
     int64_t ld_coef;
     int32_t max_iter;
 };
+// (the preconditioned variant, kPre: rr holds r.z, and the second sums -- r.r, for the norms -- lie
+// kRedBlocks * S partials after the first; the inverse diagonal is the kernels' last argument)
 
 enum CgFinal { kFinNorm = 0, kFinInit = 1, kFinAlpha = 2, kFinUpdate = 3 };
 
@@ -326,8 +330,11 @@ struct ColReduce {
 
 // finalisation of one column (called by one thread per column in the last block); the
 // scalars are rounded to T like linear_cg's (float for the reference's precision)
-template <typename T>
-__device__ inline void cg_final_column(int fin, int c, double s, const CgState &st, double *lds_norm, int *lds_conv) {
+// (kPre: s = sum r.z, what alpha and beta are made of; s2 = sum r.r, what the norms are made of)
+template <typename T, bool kPre = false>
+__device__ inline void cg_final_column(int fin, int c, double s, double s2, const CgState &st, double *lds_norm,
+                                       int *lds_conv) {
+    const double q = kPre ? s2 : s;
     if (fin == kFinNorm) {
         double nrm = (double)(T)sqrt(s);  // rhs.norm(2, dim=-2)
         const int zero = nrm < kCgEps;
@@ -335,9 +342,9 @@ __device__ inline void cg_final_column(int fin, int c, double s, const CgState &
         st.rhs_norm[c] = zero ? 1.0 : nrm;
     } else if (fin == kFinInit) {
         st.rr[c] = s;
-        const double nrm = st.rhs_zero[c] ? 0.0 : sqrt(s);
+        const double nrm = st.rhs_zero[c] ? 0.0 : sqrt(q);
         st.rnorm[c] = nrm;
-        const int cv = sqrt(s) < kStopAfter;  // (the initial check does not mask zero rhs)
+        const int cv = sqrt(q) < kStopAfter;  // (the initial check does not mask zero rhs)
         st.conv[c] = cv;
         lds_conv[c] = cv;
     } else if (fin == kFinAlpha) {
@@ -354,26 +361,36 @@ __device__ inline void cg_final_column(int fin, int c, double s, const CgState &
         // (*iters is still this iteration's k: thread 0 counts it up after the columns are final)
         if (st.coef) st.coef[((int64_t)st.max_iter + *st.iters) * st.ld_coef + c] = (double)(T)b;
         st.rr[c] = s;
-        const double nrm = st.rhs_zero[c] ? 0.0 : sqrt(s);
+        const double nrm = st.rhs_zero[c] ? 0.0 : sqrt(q);
         st.rnorm[c] = nrm;
         st.conv[c] = nrm < kStopAfter;
         lds_norm[c] = nrm;
     }
 }
 
-template <int kOp, typename T>
+// (kPre: z = dinv . r is formed here and never stored; acc = r.z, acc2 = r.r)
+template <int kOp, typename T, bool kPre = false>
 __device__ inline void cg_row_op(int64_t r, int c, int32_t S, T *R, T *P, T *Y, T *X, const T *B, int64_t ldb,
-                                 const CgState &st, double &acc) {
+                                 const CgState &st, double &acc, double &acc2, double dv) {
     const int64_t o = r * S + c;
     if constexpr (kOp == kFinNorm) {
         const double b = B[r * ldb + c];
         acc += b * b;
     } else if constexpr (kOp == kFinInit) {
         const T b = B[r * ldb + c] / (T)st.rhs_norm[c];
-        R[o] = b;
-        P[o] = b;
-        X[o] = 0.f;
-        acc += (double)b * b;
+        if constexpr (kPre) {
+            const T z = (T)dv * b;
+            R[o] = b;
+            P[o] = z;
+            X[o] = 0.f;
+            acc += (double)b * z;
+            acc2 += (double)b * b;
+        } else {
+            R[o] = b;
+            P[o] = b;
+            X[o] = 0.f;
+            acc += (double)b * b;
+        }
     } else if constexpr (kOp == kFinAlpha) {
         acc += (double)P[o] * Y[o];
     } else {
@@ -381,33 +398,50 @@ __device__ inline void cg_row_op(int64_t r, int c, int32_t S, T *R, T *P, T *Y, 
         const T rn = R[o] - a * Y[o];
         R[o] = rn;
         X[o] = X[o] + a * P[o];
-        acc += (double)rn * rn;
+        if constexpr (kPre) {
+            const T z = (T)dv * rn;
+            acc += (double)rn * z;
+            acc2 += (double)rn * rn;
+        } else {
+            acc += (double)rn * rn;
+        }
     }
 }
 
-template <int kOp, typename T>
+template <int kOp, typename T, bool kPre = false>
 __global__ __launch_bounds__(256) void cg_reduce_kernel(int64_t n, int32_t S, T *R, T *P, T *Y, T *X, const T *B,
-                                                        int64_t ldb, CgState st, int32_t k_check, double tol) {
+                                                        int64_t ldb, CgState st, int32_t k_check, double tol,
+                                                        const double *dinv) {
     if (kOp >= kFinAlpha && __builtin_nontemporal_load(st.done)) return;
-    __shared__ double red[4][kMaxRhs];
+    constexpr int kSums = kPre ? 2 : 1;  // kPre: r.z and r.r per column (the init and the update only)
+    __shared__ double red[4 * kSums][kMaxRhs];  // (sum j of wave w: red[4 * j + w])
     __shared__ double fin_norm[kMaxRhs];
     __shared__ int fin_conv[kMaxRhs];
     __shared__ uint32_t last;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    double acc[4] = {0.0, 0.0, 0.0, 0.0}, acc2[4] = {0.0, 0.0, 0.0, 0.0};
     const int64_t n_waves = (int64_t)gridDim.x * 4;
     for (int64_t r = (int64_t)blockIdx.x * 4 + w; r < n; r += n_waves) {
+        double dv = 0.0;
+        if constexpr (kPre) dv = dinv[r];
 #pragma unroll
         for (int ci = 0; ci < 4; ++ci) {
             const int c = lane + 64 * ci;
-            if (c < S) cg_row_op<kOp, T>(r, c, S, R, P, Y, X, B, ldb, st, acc[ci]);
+            if (c < S) cg_row_op<kOp, T, kPre>(r, c, S, R, P, Y, X, B, ldb, st, acc[ci], acc2[ci], dv);
         }
     }
 #pragma unroll
-    for (int ci = 0; ci < 4; ++ci) red[w][lane + 64 * ci] = acc[ci];
+    for (int ci = 0; ci < 4; ++ci) {
+        red[w][lane + 64 * ci] = acc[ci];
+        if constexpr (kPre) red[4 + w][lane + 64 * ci] = acc2[ci];
+    }
     __syncthreads();
-    for (int c = threadIdx.x; c < S; c += 256)
-        st.part[(int64_t)blockIdx.x * S + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+    for (int c = threadIdx.x; c < S; c += 256) {
+#pragma unroll
+        for (int j = 0; j < kSums; ++j)
+            st.part[((int64_t)j * kRedBlocks + blockIdx.x) * S + c] =
+                ((red[4 * j][c] + red[4 * j + 1][c]) + red[4 * j + 2][c]) + red[4 * j + 3][c];
+    }
     __threadfence();
     __syncthreads();
     if (threadIdx.x == 0) last = atomicAdd(st.ticket, 1u) == gridDim.x - 1;
@@ -417,20 +451,28 @@ __global__ __launch_bounds__(256) void cg_reduce_kernel(int64_t n, int32_t S, T 
     // the last block: column c summed over blocks in order; tpc threads per column split the
     // blocks into contiguous ranges, combined in range order
     const int tpc = max(1, 256 / S);
-    double *sum = &red[0][0];  // reuse: [tpc][S] <= 1024 doubles
+    double *sum = &red[0][0];  // reuse: [tpc][S] <= 1024 doubles per sum
     const int nb = gridDim.x;
     if ((int)threadIdx.x < tpc * S) {
         const int c = threadIdx.x % S, q = threadIdx.x / S;
         const int b0 = (int)((int64_t)nb * q / tpc), b1 = (int)((int64_t)nb * (q + 1) / tpc);
-        double s = 0.0;
-        for (int b = b0; b < b1; ++b) s += __builtin_nontemporal_load(&st.part[(int64_t)b * S + c]);
-        sum[q * S + c] = s;
+#pragma unroll
+        for (int j = 0; j < kSums; ++j) {
+            double s = 0.0;
+            for (int b = b0; b < b1; ++b)
+                s += __builtin_nontemporal_load(&st.part[((int64_t)j * kRedBlocks + b) * S + c]);
+            sum[j * 4 * kMaxRhs + q * S + c] = s;
+        }
     }
     __syncthreads();
     for (int c = threadIdx.x; c < S; c += 256) {
-        double s = 0.0;
-        for (int q = 0; q < tpc; ++q) s += sum[q * S + c];
-        cg_final_column<T>(kOp, c, s, st, fin_norm, fin_conv);
+        double s[kSums];
+#pragma unroll
+        for (int j = 0; j < kSums; ++j) {
+            s[j] = 0.0;
+            for (int q = 0; q < tpc; ++q) s[j] += sum[j * 4 * kMaxRhs + q * S + c];
+        }
+        cg_final_column<T, kPre>(kOp, c, s[0], s[kSums - 1], st, fin_norm, fin_conv);
     }
     if (threadIdx.x == 0) *st.ticket = 0u;
     if constexpr (kOp == kFinInit || kOp == kFinUpdate) {
@@ -453,13 +495,20 @@ __global__ __launch_bounds__(256) void cg_reduce_kernel(int64_t n, int32_t S, T 
 }
 
 // P = R + beta P  (curr_conjugate_vec.mul_(beta).add_(precond_residual))
-template <typename T>
-__global__ __launch_bounds__(256) void cg_dir_kernel(int64_t n, int32_t S, const T *R, T *P, CgState st) {
+// (kPre: P = z + beta P with z = dinv . R formed here)
+template <typename T, bool kPre = false>
+__global__ __launch_bounds__(256) void cg_dir_kernel(int64_t n, int32_t S, const T *R, T *P, CgState st,
+                                                     const double *dinv) {
     if (__builtin_nontemporal_load(st.done)) return;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n * S) return;
     const T b = (T)st.beta[i % S];
-    P[i] = P[i] * b + R[i];
+    if constexpr (kPre) {
+        const T z = (T)dinv[i / S] * R[i];
+        P[i] = P[i] * b + z;
+    } else {
+        P[i] = P[i] * b + R[i];
+    }
 }
 
 // result.mul(rhs_norm) into the caller's layout
@@ -484,7 +533,8 @@ struct CgLayout {
     int32_t tw1, nt1, tw2, nt2;  // column tiles of Phi_t^T (over the n_sys rows of P) and Phi_t (over W)
 };
 
-static CgLayout cg_layout(int64_t n_sys, int64_t n_cols, int32_t S, size_t elem) {
+// (n_sums = 2: the preconditioned variant's two partials per (block, column))
+static CgLayout cg_layout(int64_t n_sys, int64_t n_cols, int32_t S, size_t elem, int n_sums = 1) {
     CgLayout l{};
     size_t o = 0;
     const size_t vec = al256((size_t)n_sys * S * elem);
@@ -493,7 +543,7 @@ static CgLayout cg_layout(int64_t n_sys, int64_t n_cols, int32_t S, size_t elem)
     l.base.Y = o; o += vec;
     l.base.X = o; o += vec;
     l.W = o; o += al256((size_t)n_cols * S * elem);
-    l.base.part = o; o += al256((size_t)kRedBlocks * S * sizeof(double));
+    l.base.part = o; o += al256((size_t)n_sums * kRedBlocks * S * sizeof(double));
     l.base.dbl = o; o += al256((size_t)5 * S * sizeof(double));
     l.base.i32 = o; o += al256((size_t)(2 * S + 8) * sizeof(int32_t));
     l.tw1 = spmm_tile_rows(n_sys, S, elem);
@@ -548,7 +598,7 @@ struct CgPolyLayout {
     size_t W, H0, H1, total;
 };
 
-static CgPolyLayout cg_poly_layout(int64_t n_sys, int64_t n, int32_t S) {
+static CgPolyLayout cg_poly_layout(int64_t n_sys, int64_t n, int32_t S, int n_sums = 1) {
     CgPolyLayout l{};
     size_t o = 0;
     const size_t vec = al256((size_t)n_sys * S * sizeof(double)), blk = al256((size_t)n * S * sizeof(double));
@@ -559,7 +609,7 @@ static CgPolyLayout cg_poly_layout(int64_t n_sys, int64_t n, int32_t S) {
     l.W = o; o += blk;
     l.H0 = o; o += blk;
     l.H1 = o; o += blk;
-    l.base.part = o; o += al256((size_t)kRedBlocks * S * sizeof(double));
+    l.base.part = o; o += al256((size_t)n_sums * kRedBlocks * S * sizeof(double));
     l.base.dbl = o; o += al256((size_t)5 * S * sizeof(double));
     l.base.i32 = o; o += al256((size_t)(2 * S + 8) * sizeof(int32_t));
     l.total = o;
@@ -591,12 +641,13 @@ struct PolyMatVec {
 };
 
 // linear_cg on n_sys x n_rhs systems; `mv` computes Y = (K + s2 I) P on the stream (the checks of its own
-// operands are the caller's); `l`: where the recurrence's buffers lie in the workspace
-template <typename T, typename MatVec>
+// operands are the caller's); `l`: where the recurrence's buffers lie in the workspace.  kPre: linear_cg with
+// the preconditioner closure z = dinv . r (p = z + beta p, alpha and beta from r.z, the norms from r.r)
+template <typename T, bool kPre = false, typename MatVec>
 static int32_t cg_solve_impl(int64_t n_sys, MatVec &mv, const CgBase &l, const T *rhs, int64_t ld_rhs, int32_t n_rhs,
                              double tolerance, int32_t max_iter, T *x, int64_t ldx, void *workspace,
                              int32_t *iters_out, double *resid_out, grf_stream_t stream, double *coef = nullptr,
-                             int64_t ld_coef = 0) {
+                             int64_t ld_coef = 0, const double *dinv = nullptr) {
     hipStream_t sm = S(stream);
     char *w = (char *)workspace;
     T *R = (T *)(w + l.R), *P = (T *)(w + l.P), *Y = (T *)(w + l.Y), *X = (T *)(w + l.X);
@@ -621,9 +672,9 @@ static int32_t cg_solve_impl(int64_t n_sys, MatVec &mv, const CgBase &l, const T
     int32_t rc0;
 
     if ((rc0 = mv.prepare(w, sm)) != GRF_OK) return rc0;
-    cg_reduce_kernel<kFinNorm, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance);
+    cg_reduce_kernel<kFinNorm, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance, dinv);
     GRF_CHECK_LAUNCH("cg_reduce_kernel<norm>");
-    cg_reduce_kernel<kFinInit, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance);
+    cg_reduce_kernel<kFinInit, T, kPre><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance, dinv);
     GRF_CHECK_LAUNCH("cg_reduce_kernel<init>");
 
     int32_t *h = nullptr;  // pinned: [done of even iterations, done of odd iterations, iters]
@@ -636,9 +687,9 @@ static int32_t cg_solve_impl(int64_t n_sys, MatVec &mv, const CgBase &l, const T
         // mvms = (K + s2 I) p
         rc = mv(P, Y, Sn, st.done, sm);
         if (rc != GRF_OK) break;
-        cg_reduce_kernel<kFinAlpha, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance);
-        cg_reduce_kernel<kFinUpdate, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance);
-        cg_dir_kernel<T><<<eb, 256, 0, sm>>>(n_sys, Sn, R, P, st);
+        cg_reduce_kernel<kFinAlpha, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance, dinv);
+        cg_reduce_kernel<kFinUpdate, T, kPre><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance, dinv);
+        cg_dir_kernel<T, kPre><<<eb, 256, 0, sm>>>(n_sys, Sn, R, P, st, dinv);
         if (hipGetLastError() != hipSuccess) {
             set_error("grf_cg_gram_solve: launch failed");
             rc = GRF_EHIP;
@@ -728,6 +779,72 @@ static int32_t cg_poly_solve(int64_t n_sys, int64_t n, const int64_t *g_ptr, con
                   inv_map, noise, l};
     return cg_solve_impl<double>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace,
                                  iters_out, resid_out, stream, coef, ld_coef);
+}
+
+// ------------------------------------------------- the diagonally preconditioned solves (fp64 only)
+// dinv[r] = 1 / (sum_e Phi[row_map[r], e]^2 + noise) = 1 / diag(K^)[r]: one wave per row; the squares (fp32
+// widened: exact in fp64) are added to +0.0 one by one in the row's stored order, every lane the same sum.
+// A row whose sum plus noise is not positive (empty, zero noise) gets 1: it is not preconditioned.
+__global__ __launch_bounds__(256) void gram_jacobi_kernel(int64_t n_sel, const int64_t *ptr, const float *val,
+                                                          const int32_t *row_map, double noise, double *dinv) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_sel) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t row = uniform(row_map ? (int64_t)row_map[r] : r);
+    const int64_t e0 = uniform(ptr[row]), e1 = uniform(ptr[row + 1]);
+    double acc = 0.0;
+    for (int64_t eb = e0; eb < e1; eb += 64) {
+        const int64_t e = eb + lane;
+        const float v_l = e < e1 ? __builtin_nontemporal_load(&val[e]) : 0.f;
+        const int cnt = (int)min<int64_t>(64, e1 - eb);
+        for (int j = 0; j < cnt; ++j) {
+            const double v = (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int32_t, v_l), j));
+            acc += v * v;
+        }
+    }
+    const double d = acc + noise;
+    if (lane == 0) dinv[r] = d > 0.0 ? 1.0 / d : 1.0;
+}
+
+static int32_t pcg_gram_solve(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                              const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
+                              const float *t_val, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
+                              double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
+                              size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
+                              grf_stream_t stream, double *coef = nullptr, int64_t ld_coef = 0) {
+    GRF_REQUIRE(n_sys > 0 && n_cols > 0 && ptr && t_ptr && rhs && x && dinv, GRF_EINVAL,
+                "grf_pcg_gram_solve: bad arguments");
+    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_pcg_gram_solve: n_rhs must be in [1, %d]",
+                kMaxRhs);
+    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_pcg_gram_solve: bad strides");
+    const CgLayout l = cg_layout(n_sys, n_cols, n_rhs, sizeof(double), 2);
+    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL,
+                "grf_pcg_gram_solve: workspace too small (%zu < %zu)", workspace_bytes, l.total);
+    GramMatVec<double> mv{n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, l};
+    return cg_solve_impl<double, true>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace,
+                                       iters_out, resid_out, stream, coef, ld_coef, dinv);
+}
+
+static int32_t pcg_poly_solve(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                              const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
+                              const double *f, int32_t n_f, const int32_t *row_map, const int32_t *inv_map,
+                              double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs, double tolerance,
+                              int32_t max_iter, double *x, int64_t ldx, void *workspace, size_t workspace_bytes,
+                              int32_t *iters_out, double *resid_out, const double *dinv, grf_stream_t stream,
+                              double *coef = nullptr, int64_t ld_coef = 0) {
+    GRF_REQUIRE(n_sys > 0 && n > 0 && g_ptr && gt_ptr && f && n_f >= 1 && row_map && inv_map && rhs && x && dinv,
+                GRF_EINVAL, "grf_pcg_poly_solve: bad arguments");
+    GRF_REQUIRE(n < (1ll << 31) && n_sys < (1ll << 31), GRF_EUNSUPPORTED, "grf_pcg_poly_solve: more than 2^31 rows");
+    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_pcg_poly_solve: n_rhs must be in [1, %d]",
+                kMaxRhs);
+    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_pcg_poly_solve: bad strides");
+    const CgPolyLayout l = cg_poly_layout(n_sys, n, n_rhs, 2);
+    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL,
+                "grf_pcg_poly_solve: workspace too small (%zu < %zu)", workspace_bytes, l.total);
+    PolyMatVec mv{n_sys, PolyOp{n, g_ptr, g_idx, g_val, f, n_f}, PolyOp{n, gt_ptr, gt_idx, gt_val, f, n_f}, row_map,
+                  inv_map, noise, l};
+    return cg_solve_impl<double, true>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace,
+                                       iters_out, resid_out, stream, coef, ld_coef, dinv);
 }
 
 }  // namespace grf
@@ -872,6 +989,74 @@ int32_t grf_cg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g
     return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
                          ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
                          stream, coef, ld_coef);
+}
+
+int32_t grf_gram_jacobi_f64(int64_t n_sel, const int64_t *ptr, const int32_t *idx, const float *val,
+                            const int32_t *row_map, double noise, double *dinv, grf_stream_t stream) {
+    (void)idx;  // (the diagonal needs no columns; the argument keeps the CSR triple together)
+    GRF_REQUIRE(n_sel >= 0 && ptr && (dinv || n_sel == 0), GRF_EINVAL, "grf_gram_jacobi_f64: bad arguments");
+    GRF_REQUIRE(noise >= 0.0, GRF_EINVAL, "grf_gram_jacobi_f64: the noise must not be negative");
+    if (n_sel == 0) return GRF_OK;
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n_sel, 4), 256, "gram_jacobi_kernel");
+    gram_jacobi_kernel<<<(unsigned)cdiv<int64_t>(n_sel, 4), 256, 0, S(stream)>>>(n_sel, ptr, val, row_map, noise, dinv);
+    GRF_CHECK_LAUNCH("gram_jacobi_kernel");
+    return GRF_OK;
+}
+
+size_t grf_pcg_workspace_bytes(int64_t n_sys, int64_t n_cols, int32_t n_rhs) {
+    return cg_layout(n_sys, n_cols, n_rhs, sizeof(double), 2).total;
+}
+
+int32_t grf_pcg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                               const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
+                               const float *t_val, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
+                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
+                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
+                               grf_stream_t stream) {
+    return pcg_gram_solve(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs, n_rhs,
+                          tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out, dinv, stream);
+}
+
+int32_t grf_pcg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                                       const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr,
+                                       const int32_t *t_idx, const float *t_val, double noise, const double *rhs,
+                                       int64_t ld_rhs, int32_t n_rhs, double tolerance, int32_t max_iter, double *x,
+                                       int64_t ldx, void *workspace, size_t workspace_bytes, int32_t *iters_out,
+                                       double *resid_out, double *coef, int64_t ld_coef, const double *dinv,
+                                       grf_stream_t stream) {
+    GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_pcg_gram_solve_lanczos_f64: bad coefficient buffer");
+    return pcg_gram_solve(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs, n_rhs,
+                          tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out, dinv, stream,
+                          coef, ld_coef);
+}
+
+size_t grf_pcg_poly_workspace_bytes(int64_t n_sys, int64_t n, int32_t n_rhs) {
+    return cg_poly_layout(n_sys, n, n_rhs, 2).total;
+}
+
+int32_t grf_pcg_poly_solve_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                               const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
+                               const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
+                               const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
+                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
+                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
+                               grf_stream_t stream) {
+    return pcg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
+                          ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
+                          dinv, stream);
+}
+
+int32_t grf_pcg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                                       const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
+                                       const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
+                                       const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs,
+                                       int32_t n_rhs, double tolerance, int32_t max_iter, double *x, int64_t ldx,
+                                       void *workspace, size_t workspace_bytes, int32_t *iters_out, double *resid_out,
+                                       double *coef, int64_t ld_coef, const double *dinv, grf_stream_t stream) {
+    GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_pcg_poly_solve_lanczos_f64: bad coefficient buffer");
+    return pcg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
+                          ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
+                          dinv, stream, coef, ld_coef);
 }
 
 #pragma GCC visibility pop

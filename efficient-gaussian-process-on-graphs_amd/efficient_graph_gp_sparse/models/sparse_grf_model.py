@@ -33,6 +33,11 @@ except ImportError:  # pragma: no cover - depends on the environment
 EVAL_CG_TOLERANCE = 1e-2  # gpytorch.settings.eval_cg_tolerance: the solves of a prediction
 
 
+def _check_preconditioner(preconditioner, what: str) -> None:
+    if preconditioner is not None and preconditioner != "jacobi":
+        raise ValueError(f"{what}: preconditioner must be None or \"jacobi\", not {preconditioner!r}")
+
+
 def _noise_value(likelihood) -> float:
     noise = likelihood.noise if hasattr(likelihood, "noise") else likelihood
     return float(noise.item() if torch.is_tensor(noise) else noise)
@@ -67,25 +72,31 @@ class SparseGraphGP(_Base):
         return phi
 
     def marginal_log_likelihood(self, probes=None, n_probes=64, generator=None, tolerance=None, max_iter=1000,
-                                per_datum=True):
+                                per_datum=True, preconditioner=None):
         """The training objective the reference evaluates as ``mll(model(x_train), y_train)`` under
         ``max_cholesky_size(0)``: the marginal log-likelihood of ``y_train`` (zero mean) by CG and stochastic
         Lanczos quadrature, K never formed (``grf_amd.features.grf_marginal_log_likelihood``).  A
         differentiable fp64 scalar: ``backward()`` fills the modulator's gradient and, when the likelihood's
         noise is a tensor, the noise's (a float noise is a constant).  ``per_datum`` divides by the number
-        of training points, as ``ExactMarginalLogLikelihood`` does."""
+        of training points, as ``ExactMarginalLogLikelihood`` does.  ``preconditioner="jacobi"`` preconditions the
+        solve by diag(K^) (None, the default: the reference's unpreconditioned solve)."""
         noise = self.likelihood.noise if hasattr(self.likelihood, "noise") else self.likelihood
         info = {}
         out = grf_marginal_log_likelihood(
             self.covar_module.modulator_vector, noise, self.covar_module._step_set(), self.x_train.int().flatten(),
             self.y_train, probes=probes, n_probes=n_probes, generator=generator, tolerance=tolerance,
-            max_iter=max_iter, per_datum=per_datum, info=info)
+            max_iter=max_iter, per_datum=per_datum, info=info, preconditioner=preconditioner)
         self.last_cg_iterations = info["cg_iterations"]
         return out
 
     @torch.no_grad()
-    def predict(self, x_test, n_samples=64, cg_dtype=torch.float64, max_iter=1000, tolerance=None):
-        """(n_samples x n_test) posterior samples (float32, like the reference)."""
+    def predict(self, x_test, n_samples=64, cg_dtype=torch.float64, max_iter=1000, tolerance=None,
+                preconditioner=None):
+        """(n_samples x n_test) posterior samples (float32, like the reference).  ``preconditioner="jacobi"``
+        preconditions the solve by diag(K^) (fp64 only: with ``cg_dtype=torch.float32`` a ValueError)."""
+        _check_preconditioner(preconditioner, "predict")
+        if preconditioner is not None and cg_dtype != torch.float64:
+            raise ValueError("predict: preconditioner=\"jacobi\" needs cg_dtype=torch.float64")
         dev = x_test.device
         train_indices = self.x_train.int().flatten()
         test_indices = x_test.int().flatten()
@@ -104,10 +115,11 @@ class SparseGraphGP(_Base):
         out, self.last_cg_iterations = eng.pathwise_predict(
             phi, train_indices.to(eng.device), test_indices.to(eng.device), self.y_train, noise_variance,
             eps1_batch, eps2_batch, tolerance=tolerance, max_iter=max_iter, dtype=cg_dtype,
-            f=self.covar_module.modulator_vector if op is not None else None)
+            f=self.covar_module.modulator_vector if op is not None else None, preconditioner=preconditioner)
         return out.to(torch.float32)
 
-    def _moments(self, x_test, full_cov, tolerance, max_iter, add_noise):
+    def _moments(self, x_test, full_cov, tolerance, max_iter, add_noise, preconditioner=None):
+        _check_preconditioner(preconditioner, "predict_f")
         dev = x_test.device
         eng = get_engine(dev if dev.type == "cuda" else None)
         op = self.covar_module._operator()
@@ -119,12 +131,12 @@ class SparseGraphGP(_Base):
             phi, self.x_train.int().flatten().to(eng.device), x_test.int().flatten().to(eng.device), self.y_train,
             _noise_value(self.likelihood), f=self.covar_module.modulator_vector if op is not None else None,
             full_cov=full_cov, tolerance=EVAL_CG_TOLERANCE if tolerance is None else float(tolerance),
-            max_iter=max_iter, info=info, add_noise=add_noise)
+            max_iter=max_iter, info=info, add_noise=add_noise, preconditioner=preconditioner)
         self.last_cg_iterations = max(info["cg_iterations"] + [info["alpha_iterations"]])
         return out
 
     @torch.no_grad()
-    def predict_f(self, x_test, full_cov=False, tolerance=None, max_iter=1000):
+    def predict_f(self, x_test, full_cov=False, tolerance=None, max_iter=1000, preconditioner=None):
         """The exact posterior mean and variance of the latent function at ``x_test``: (mean, var), fp64
         tensors of shape (n_test,), or with ``full_cov`` (mean, cov) with cov (n_test x n_test) -- what the
         reference's dense baseline returns from ``model.predict_f`` (run_scaling_experiment.py:729) and its
@@ -143,20 +155,21 @@ class SparseGraphGP(_Base):
         x_k^T (2 b - K^ x_k) = b^T K^-1 b - ||x - x_k||^2_K, which is below b^T K^-1 b for any x_k at the cost of
         one more operator product per chunk.
         ``last_cg_iterations`` is the largest iteration count over the chunks' solves and the solve for the
-        mean."""
-        return self._moments(x_test, full_cov, tolerance, max_iter, False)
+        mean.  ``preconditioner="jacobi"`` preconditions every solve by diag(K^), built once per call; the
+        energy form's bound holds for any iterate, so the statement on the variances is unchanged."""
+        return self._moments(x_test, full_cov, tolerance, max_iter, False, preconditioner)
 
     @torch.no_grad()
-    def predict_y(self, x_test, full_cov=False, tolerance=None, max_iter=1000):
+    def predict_y(self, x_test, full_cov=False, tolerance=None, max_iter=1000, preconditioner=None):
         """``predict_f`` for the noisy observation: the noise variance added to the variances, or to the
         covariance's diagonal."""
-        return self._moments(x_test, full_cov, tolerance, max_iter, True)
+        return self._moments(x_test, full_cov, tolerance, max_iter, True, preconditioner)
 
     @torch.no_grad()
-    def nlpd(self, x_test, y_test, tolerance=None, max_iter=1000):
+    def nlpd(self, x_test, y_test, tolerance=None, max_iter=1000, preconditioner=None):
         """The negative log predictive density of ``y_test`` under ``predict_y``'s marginals, by the reference's
         formula (wind_experiment.py:319-324): an fp64 scalar tensor."""
-        mean, var = self.predict_y(x_test, tolerance=tolerance, max_iter=max_iter)
+        mean, var = self.predict_y(x_test, tolerance=tolerance, max_iter=max_iter, preconditioner=preconditioner)
         y = y_test.to(mean.device, torch.float64).flatten()
         std = var.sqrt()
         z = (y - mean) / std

@@ -194,6 +194,19 @@ SIGNATURES = {
     "grf_posterior_rhs_f64": (_i32, [_i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
     "grf_posterior_reduce_workspace_bytes": (_sz, [_i64, _i32]),
     "grf_posterior_reduce_f64": (_i32, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _dbl, _vp, _vp, _vp, _sz, _vp]),
+    # the diagonally preconditioned solves: the unpreconditioned lists with dinv before the stream
+    "grf_gram_jacobi_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _dbl, _vp, _vp]),
+    "grf_pcg_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "grf_pcg_gram_solve_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _dbl, _vp, _i64, _i32, _dbl,
+                                      _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "grf_pcg_gram_solve_lanczos_f64": (_i32, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _dbl, _vp, _i64, _i32,
+                                              _dbl, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "grf_pcg_poly_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "grf_pcg_poly_solve_f64": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _dbl, _vp, _i64,
+                                      _i32, _dbl, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "grf_pcg_poly_solve_lanczos_f64": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _dbl,
+                                              _vp, _i64, _i32, _dbl, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp, _i64,
+                                              _vp, _vp]),
 }
 
 _lib = None

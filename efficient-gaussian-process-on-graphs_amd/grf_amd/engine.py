@@ -1167,16 +1167,60 @@ class GRFEngine:
             Y.add_(V, alpha=float(noise))
         return Y
 
+    def _precond(self, precond, n_sys: int, B: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+        """The checked inverse diagonal of a preconditioned solve (None: the plain solve)."""
+        if precond is None:
+            return None
+        if B.dtype != torch.float64:
+            raise ValueError(f"{what}: a preconditioned solve needs a float64 B")
+        if not isinstance(precond, torch.Tensor) or precond.dtype != torch.float64 or precond.numel() != n_sys:
+            raise ValueError(f"{what}: precond must be a float64 tensor of {n_sys} inverse diagonal entries")
+        return precond.to(self.device).flatten().contiguous()
+
+    @staticmethod
+    def _preconditioner_name(preconditioner, what: str) -> bool:
+        """True for "jacobi", False for None; anything else is refused."""
+        if preconditioner is None:
+            return False
+        if isinstance(preconditioner, str) and preconditioner == "jacobi":
+            return True
+        raise ValueError(f"{what}: preconditioner must be None or \"jacobi\", not {preconditioner!r}")
+
+    def gram_jacobi(self, phi: DeviceCSR, rows=None, noise: float = 0.0) -> torch.Tensor:
+        """dinv[r] = 1 / (sum_e Phi[rows[r], e]^2 + noise) = 1 / diag(Phi_T Phi_T^T + noise I)[r], fp64 on the
+        device (grf_gram_jacobi_f64): the Jacobi preconditioner of ``cg_solve(precond=...)``.  The squares are
+        summed in the row's stored order; a row whose sum plus noise is not positive gets 1."""
+        if phi.val32 is None:
+            raise ValueError("gram_jacobi: Phi needs its float32 values (val32)")
+        rmap = self._row_map(rows)
+        n_sel = phi.n_rows if rmap is None else rmap.numel()
+        dinv = self._empty(n_sel, torch.float64)
+        C.check(self.lib.grf_gram_jacobi_f64(n_sel, _p(phi.ptr), _p(phi.idx), _p(phi.val32), _p(rmap), float(noise),
+                                             _p(dinv), self.stream), "grf_gram_jacobi_f64")
+        return dinv
+
+    def poly_jacobi(self, op: WalkPolynomial, f, rows, noise: float) -> torch.Tensor:
+        """The same inverse diagonal for the exact kernel: 1 / (poly_kernel_diag(op, f, x=rows) + noise).  Correct
+        but dear -- the diagonal costs len(rows) / 256 operator chains, about as much as that many CG
+        iterations -- and the exact kernel is well conditioned, so this mostly serves as the default behind
+        ``preconditioner="jacobi"``; pass an explicit ``precond`` vector where a cheaper diagonal is at hand."""
+        d = self.poly_kernel_diag(op, f, x=rows) + float(noise)
+        return torch.where(d > 0, 1.0 / d, torch.ones_like(d))
+
     def cg_solve(self, phi: DeviceCSR, B: torch.Tensor, noise: float, rows=None, phi_t: Optional[DeviceCSR] = None,
                  tolerance: float = 1.0, max_iter: int = 1000, return_residuals: bool = False,
-                 return_lanczos: bool = False):
+                 return_lanczos: bool = False, precond: Optional[torch.Tensor] = None):
         """linear_cg on (Phi[rows] Phi[rows]^T + noise I) X = B for the columns of B (n x S, S <= 256).
 
         B float64 runs the recurrence in fp64, float32 in the reference's fp32.  Returns
         (X, iterations) [+ the final residual norms of the normalised columns].  tolerance / max_iter default to gpytorch's settings.cg_tolerance (1)
         and settings.max_cg_iterations (1000).  return_lanczos (fp64 only) appends the CG coefficients, a
         (2 max_iter x S) fp64 device tensor: row k holds alpha_k of every column, row max_iter + k its
-        beta_k, zero for the iterations that did not run (the Lanczos tridiagonals come from these)."""
+        beta_k, zero for the iterations that did not run (the Lanczos tridiagonals come from these).
+        precond (fp64 only): the inverse diagonal ``dinv`` (n,) of a diagonal preconditioner, e.g.
+        ``gram_jacobi(phi, rows, noise)``: linear_cg with the closure z = dinv . r (grf_pcg_gram_solve_f64); the
+        residual norms and the stopping rule stay those of the unpreconditioned residual, and the coefficients
+        are then the Lanczos coefficients of D^-1/2 K^ D^-1/2.  Ones reproduce the plain solve bit for bit."""
         rmap = self._row_map(rows)
         n_sys = phi.n_rows if rmap is None else rmap.numel()
         if B.dtype not in (torch.float32, torch.float64) or B.dim() != 2 or B.stride(1) != 1 \
@@ -1184,10 +1228,12 @@ class GRFEngine:
             raise ValueError("cg_solve: B must be a float32/float64 (n_rows x S) row-major matrix")
         if return_lanczos and B.dtype != torch.float64:
             raise ValueError("cg_solve: return_lanczos needs a float64 B")
+        dinv = self._precond(precond, n_sys, B, "cg_solve")
         phi_t = self.csr_transpose(phi, rmap) if phi_t is None else phi_t
         S = B.shape[1]
         X = torch.empty((n_sys, S), dtype=B.dtype, device=self.device)
-        ws = self._ws(self.lib.grf_cg_workspace_bytes(n_sys, phi.n_cols, S))
+        wsb = self.lib.grf_cg_workspace_bytes if dinv is None else self.lib.grf_pcg_workspace_bytes
+        ws = self._ws(wsb(n_sys, phi.n_cols, S))
         iters = ctypes.c_int32(0)
         resid = np.zeros(S, np.float64)
         head = (n_sys, _p(phi.ptr), _p(phi.idx), _p(phi.val32), _p(rmap), phi.n_cols, _p(phi_t.ptr),
@@ -1197,8 +1243,14 @@ class GRFEngine:
         coef = None
         if return_lanczos:
             coef = torch.empty((2 * max(int(max_iter), 0), S), dtype=torch.float64, device=self.device)
-            C.check(self.lib.grf_cg_gram_solve_lanczos_f64(*head, _p(coef), S, self.stream),
-                    "grf_cg_gram_solve_lanczos_f64")
+            if dinv is not None:
+                C.check(self.lib.grf_pcg_gram_solve_lanczos_f64(*head, _p(coef), S, _p(dinv), self.stream),
+                        "grf_pcg_gram_solve_lanczos_f64")
+            else:
+                C.check(self.lib.grf_cg_gram_solve_lanczos_f64(*head, _p(coef), S, self.stream),
+                        "grf_cg_gram_solve_lanczos_f64")
+        elif dinv is not None:
+            C.check(self.lib.grf_pcg_gram_solve_f64(*head, _p(dinv), self.stream), "grf_pcg_gram_solve_f64")
         else:
             fn = self.lib.grf_cg_gram_solve if B.dtype == torch.float32 else self.lib.grf_cg_gram_solve_f64
             C.check(fn(*head, self.stream), "grf_cg_gram_solve")
@@ -1283,19 +1335,23 @@ class GRFEngine:
         return Y
 
     def cg_solve_poly(self, op: WalkPolynomial, f, B: torch.Tensor, noise: float, rows, tolerance: float = 1.0,
-                      max_iter: int = 1000, return_residuals: bool = False, return_lanczos: bool = False):
+                      max_iter: int = 1000, return_residuals: bool = False, return_lanczos: bool = False,
+                      precond: Optional[torch.Tensor] = None):
         """``cg_solve`` on (S_T p(G) p(G)^T S_T^T + noise I) X = B for the training nodes ``rows`` (fp64): the
-        same recurrence and return shape, every matvec two Horner chains with the walk matrix."""
+        same recurrence and return shape, every matvec two Horner chains with the walk matrix.  ``precond``: the
+        inverse diagonal of a diagonal preconditioner, as in ``cg_solve`` (grf_pcg_poly_solve_f64)."""
         ft, n_f = self._poly_f(op, f)
         rmap = self._row_map(rows)
         if rmap is None:
             rmap = torch.arange(op.shape[0], dtype=torch.int32, device=self.device)
         n_sys, n = rmap.numel(), op.shape[0]
         self._check_block(B, n_sys, "cg_solve_poly: B")
+        dinv = self._precond(precond, n_sys, B, "cg_solve_poly")
         inv = self._inv_map(rmap, n)
         S = B.shape[1]
         X = torch.empty((n_sys, S), dtype=torch.float64, device=self.device)
-        ws = self._ws(self.lib.grf_cg_poly_workspace_bytes(n_sys, n, S))
+        wsb = self.lib.grf_cg_poly_workspace_bytes if dinv is None else self.lib.grf_pcg_poly_workspace_bytes
+        ws = self._ws(wsb(n_sys, n, S))
         iters = ctypes.c_int32(0)
         resid = np.zeros(S, np.float64)
         G, Gt = op.G, op.Gt
@@ -1305,8 +1361,14 @@ class GRFEngine:
         coef = None
         if return_lanczos:
             coef = torch.empty((2 * max(int(max_iter), 0), S), dtype=torch.float64, device=self.device)
-            C.check(self.lib.grf_cg_poly_solve_lanczos_f64(*head, _p(coef), S, self.stream),
-                    "grf_cg_poly_solve_lanczos_f64")
+            if dinv is not None:
+                C.check(self.lib.grf_pcg_poly_solve_lanczos_f64(*head, _p(coef), S, _p(dinv), self.stream),
+                        "grf_pcg_poly_solve_lanczos_f64")
+            else:
+                C.check(self.lib.grf_cg_poly_solve_lanczos_f64(*head, _p(coef), S, self.stream),
+                        "grf_cg_poly_solve_lanczos_f64")
+        elif dinv is not None:
+            C.check(self.lib.grf_pcg_poly_solve_f64(*head, _p(dinv), self.stream), "grf_pcg_poly_solve_f64")
         else:
             C.check(self.lib.grf_cg_poly_solve_f64(*head, self.stream), "grf_cg_poly_solve_f64")
         return (X, int(iters.value)) + ((resid,) if return_residuals else ()) + ((coef,) if return_lanczos else ())
@@ -1566,7 +1628,8 @@ class GRFEngine:
         return total / t
 
     def marginal_log_likelihood(self, steps, f: torch.Tensor, train_idx, y: torch.Tensor, noise: float,
-                                probes: torch.Tensor, tolerance: float = 1.0, max_iter: int = 1000):
+                                probes: torch.Tensor, tolerance: float = 1.0, max_iter: int = 1000,
+                                preconditioner=None):
         """MLL(f, s2) = -1/2 y^T K^-1 y - 1/2 log det K^ - n/2 log 2 pi with K^ = Phi_T Phi_T^T + s2 I,
         Phi = sum_l f_l M_l, and its gradient, K never formed (fp64): one CG solve of [y | Z] for the
         probes Z (n_train x t, t <= 255), log det by stochastic Lanczos quadrature from the solve's own
@@ -1574,6 +1637,15 @@ class GRFEngine:
             1/2 a^T dK a - 1/(2t) sum_i u_i^T dK z_i,   a = K^-1 y, u_i = K^-1 z_i.
         ``steps``: a features.StepMatrices, or a WalkPolynomial (Phi = p(G), the exact kernel: the same
         estimator on cg_solve_poly and poly_grad, neither Phi nor a power of G formed).
+        ``preconditioner="jacobi"``: the solve is preconditioned by D = diag(K^) (gram_jacobi; for a
+        WalkPolynomial poly_jacobi, which costs n_train / 256 operator chains).  ``probes`` stay the caller's
+        standard-normal g_i: the solve's columns are [y | D^1/2 g_i], whose preconditioned coefficients are the
+        Lanczos coefficients of D^-1/2 K^ D^-1/2 started at g_i / ||g_i||, so
+            log det K^ ~ sum_r log d_r + slq_logdet(coef, iters, ||g_i||^2),
+        and with z_i = D^1/2 g_i (covariance D), u_i = K^-1 z_i, tr(K^-1 dK) ~ (1/t) sum_i u_i^T dK (D^-1 z_i):
+        the gradient's probe columns become D^-1/2 g_i.  D is held constant (unbiased for any fixed D > 0).
+        The noise gradient's a.a comes from one more one-column solve (see _mll_jacobi); the iteration count
+        returned is the main solve's.
         Returns (value (float), d/df ((min(len(f), L),) fp64 device tensor), d/ds2 (float), CG iterations)."""
         tr = self._row_map(train_idx)
         n = tr.numel()
@@ -1583,13 +1655,19 @@ class GRFEngine:
         t = probes.shape[1]
         if not 1 <= t <= 255:
             raise ValueError("marginal_log_likelihood: between 1 and 255 probes per call")
-        rhs = torch.cat([yv[:, None], probes.detach().to(self.device, torch.float64)], dim=1).contiguous()
+        jacobi = self._preconditioner_name(preconditioner, "marginal_log_likelihood")
+        G = probes.detach().to(self.device, torch.float64)
         poly = isinstance(steps, WalkPolynomial)
+        if not poly:
+            phi = steps.phi(f)
+            phi_t = self.csr_transpose(phi, tr)
+        if jacobi:
+            return self._mll_jacobi(steps, f, tr, yv, noise, G, tolerance, max_iter,
+                                    None if poly else (phi, phi_t))
+        rhs = torch.cat([yv[:, None], G], dim=1).contiguous()
         if poly:
             X, iters, coef = self.cg_solve_poly(steps, f, rhs, noise, tr, tolerance, max_iter, return_lanczos=True)
         else:
-            phi = steps.phi(f)
-            phi_t = self.csr_transpose(phi, tr)
             X, iters, coef = self.cg_solve(phi, rhs, noise, tr, phi_t, tolerance, max_iter, return_lanczos=True)
         # the weighted column sums both scalars need, one host read with the coefficients' probe columns
         wt = torch.full((1 + t,), -0.5 / t, dtype=torch.float64, device=self.device)
@@ -1610,9 +1688,54 @@ class GRFEngine:
         g_f = self.steps_frob(steps, tr, X, WX, Bm, WB, wt, n_steps=n_f)
         return float(value), g_f, float(g_noise), iters
 
+    def _mll_jacobi(self, steps, f, tr, yv, noise, G, tolerance, max_iter, phis):
+        """marginal_log_likelihood's Jacobi route (see there); phis = (Phi, Phi_T^T), or None for the operator."""
+        n, t = G.shape
+        if phis is None:
+            dinv = self.poly_jacobi(steps, f, tr, noise)
+        else:
+            phi, phi_t = phis
+            dinv = self.gram_jacobi(phi, tr, noise)
+        sq = torch.sqrt(dinv)[:, None]                                         # D^-1/2
+        rhs = torch.cat([yv[:, None], G / sq], dim=1).contiguous()             # [y | D^1/2 g_i]
+        if phis is None:
+            X, iters, coef = self.cg_solve_poly(steps, f, rhs, noise, tr, tolerance, max_iter, return_lanczos=True,
+                                                precond=dinv)
+        else:
+            X, iters, coef = self.cg_solve(phi, rhs, noise, tr, phi_t, tolerance, max_iter, return_lanczos=True,
+                                           precond=dinv)
+        Bm = torch.cat([X[:, :1], G * sq], dim=1).contiguous()                 # [a | D^-1 z_i = D^-1/2 g_i]
+        wt = torch.full((1 + t,), -0.5 / t, dtype=torch.float64, device=self.device)
+        wt[0] = 0.5
+        # a.a for the noise gradient: a_k.a_k is of second order in the iterate's error under plain CG (K^-1 a_k
+        # stays in the Krylov space up to a multiple of a) but of first order under a preconditioner, so it is taken
+        # as a_k.a_k + 2 w.r_k with r_k = y - K^ a_k and w ~ K^-1 a_k from one more one-column solve:
+        # y^T K^-1 a_k = a_k.a_k + w.r_k and a_k.(a - a_k) = w.r_k, each up to a product of two solve errors
+        a = X[:, :1].contiguous()
+        if phis is None:
+            r = yv[:, None] - self.poly_gram_matvec(steps, f, a, rows=tr, cols=tr, noise=noise)
+            w, _ = self.cg_solve_poly(steps, f, a, noise, tr, tolerance, max_iter, precond=dinv)
+        else:
+            r = yv[:, None] - self.gram_matvec(phi, a, rows=tr, cols=tr, phi_t=phi_t, noise=noise)
+            w, _ = self.cg_solve(phi, a, noise, tr, phi_t, tolerance, max_iter, precond=dinv)
+        quad = (Bm * X).sum(0)
+        quad[0] = quad[0] + 2.0 * (w * r).sum()
+        cols = torch.stack([(rhs * X).sum(0), quad, torch.cat([dinv.log().sum()[None], (G * G).sum(0)])])
+        cols = cols.cpu().numpy()
+        logdet = -cols[2, 0] + self.slq_logdet(coef[:, 1:].cpu().numpy(), iters, cols[2, 1:])
+        value = -0.5 * cols[0, 0] - 0.5 * logdet - 0.5 * n * float(np.log(2.0 * np.pi))
+        g_noise = 0.5 * cols[1, 0] - 0.5 / t * float(cols[1, 1:].sum())
+        if phis is None:
+            return float(value), self.poly_grad(steps, f, tr, X, Bm, wt), float(g_noise), iters
+        WX = self.spmm(phi_t, X)
+        WB = self.spmm(phi_t, Bm)
+        n_f = min(int(f.numel()), steps.L)
+        g_f = self.steps_frob(steps, tr, X, WX, Bm, WB, wt, n_steps=n_f)
+        return float(value), g_f, float(g_noise), iters
+
     def pathwise_predict(self, phi: DeviceCSR, train_idx, test_idx, y_train: torch.Tensor, noise: float,
                          eps1: torch.Tensor, eps2: torch.Tensor, tolerance: float = 1.0, max_iter: int = 1000,
-                         dtype: torch.dtype = torch.float64, f=None):
+                         dtype: torch.dtype = torch.float64, f=None, preconditioner=None):
         """SparseGraphGP.predict (models/sparse_grf_model.py:21-45) given its random draws.
 
         phi: Phi as a DeviceCSR, or a WalkPolynomial with its modulator ``f`` (fp64 only): f_train and
@@ -1621,10 +1744,13 @@ class GRFEngine:
 
         eps1: (S x n_nodes) prior weights, eps2: (S x n_train) noise draws (already scaled by
         the noise std).  dtype: float64 (default) or the reference's float32 for every dense
-        block and the CG recurrence.  Returns (S x n_test) posterior samples (dtype) and the
-        CG iteration count."""
+        block and the CG recurrence.  ``preconditioner="jacobi"`` (float64 only) preconditions the solve
+        by diag(K^).  Returns (S x n_test) posterior samples (dtype) and the CG iteration count."""
         tr = self._row_map(train_idx)
         te = self._row_map(test_idx)
+        jacobi = self._preconditioner_name(preconditioner, "pathwise_predict")
+        if jacobi and dtype != torch.float64:
+            raise ValueError("pathwise_predict: a preconditioned solve runs in float64 only")
         if isinstance(phi, WalkPolynomial):
             if f is None or dtype != torch.float64:
                 raise ValueError("pathwise_predict: a WalkPolynomial needs its modulator f and dtype float64")
@@ -1632,7 +1758,8 @@ class GRFEngine:
             FE = self.poly_apply(phi, f, E)                                    # p(G) E: every node's prior draw
             y = y_train.to(self.device, dtype).flatten()
             B = y[:, None] - (FE[tr.long()] + eps2.to(self.device, dtype).t())
-            V, iters = self.cg_solve_poly(phi, f, B.contiguous(), noise, tr, tolerance, max_iter)
+            V, iters = self.cg_solve_poly(phi, f, B.contiguous(), noise, tr, tolerance, max_iter,
+                                          precond=self.poly_jacobi(phi, f, tr, noise) if jacobi else None)
             out = FE[te.long()] + self.poly_gram_matvec(phi, f, V, rows=te, cols=tr)
             return out.t(), iters
         E = eps1.to(self.device, dtype).t().contiguous()                      # n_nodes x S
@@ -1641,7 +1768,8 @@ class GRFEngine:
         y = y_train.to(self.device, dtype).flatten()
         B = y[:, None] - (f_train + eps2.to(self.device, dtype).t())          # b_batch^T
         phi_t = self.csr_transpose(phi, tr)
-        V, iters = self.cg_solve(phi, B.contiguous(), noise, tr, phi_t, tolerance, max_iter)
+        V, iters = self.cg_solve(phi, B.contiguous(), noise, tr, phi_t, tolerance, max_iter,
+                                 precond=self.gram_jacobi(phi, tr, noise) if jacobi else None)
         out = f_test + self.spmm(phi, self.spmm(phi_t, V), te)                # + K_test_train v
         return out.t(), iters
 
@@ -1698,7 +1826,7 @@ class GRFEngine:
 
     def posterior_moments(self, phi, train_idx, test_idx, y_train: torch.Tensor, noise: float, *, f=None,
                           full_cov: bool = False, tolerance: float = 1e-2, max_iter: int = 1000,
-                          info: Optional[dict] = None, add_noise: bool = False):
+                          info: Optional[dict] = None, add_noise: bool = False, preconditioner=None):
         """The exact posterior mean and variance of the GP at ``test_idx`` (what the reference's dense baseline
         calls predict_f, run_scaling_experiment.py:729), K never formed: with K^ = K[T,T] + noise I,
         alpha = K^-1 y and b_c = K[T, x_c],
@@ -1715,7 +1843,11 @@ class GRFEngine:
 
         phi: Phi as a DeviceCSR (rhs -> spmm -> cg_solve -> reduce per chunk), or a WalkPolynomial with its
         modulator ``f`` (poly_kernel_block / poly_kernel_diag / cg_solve_poly, then the same reduce kernel).
-        ``info`` receives ``cg_iterations`` (a list, one count per chunk) and ``alpha_iterations``."""
+        ``info`` receives ``cg_iterations`` (a list, one count per chunk) and ``alpha_iterations``.
+        ``preconditioner="jacobi"``: 1 / diag(K^) is built once and preconditions every solve (alpha and each
+        chunk); the energy form bounds b^T K^-1 b from below for any x, so the statement on the variances holds
+        for the preconditioned iterates unchanged."""
+        jacobi = self._preconditioner_name(preconditioner, "posterior_moments")
         poly = isinstance(phi, WalkPolynomial)
         if poly and f is None:
             raise ValueError("posterior_moments: a WalkPolynomial needs its modulator f")
@@ -1736,13 +1868,17 @@ class GRFEngine:
             info["cg_iterations"], info["alpha_iterations"] = iters, 0
         if ns == 0:
             return mean, (torch.empty((0, 0), dtype=torch.float64, device=self.device) if full_cov else var)
-        phi_t, alpha = None, None
+        phi_t, alpha, dinv = None, None, None
         if n:
             if poly:
-                alpha, alpha_iters = self.cg_solve_poly(phi, f, y[:, None].contiguous(), noise, tr, tolerance, max_iter)
+                dinv = self.poly_jacobi(phi, f, tr, noise) if jacobi else None
+                alpha, alpha_iters = self.cg_solve_poly(phi, f, y[:, None].contiguous(), noise, tr, tolerance, max_iter,
+                                                        precond=dinv)
             else:
                 phi_t = self.csr_transpose(phi, tr)
-                alpha, alpha_iters = self.cg_solve(phi, y[:, None].contiguous(), noise, tr, phi_t, tolerance, max_iter)
+                dinv = self.gram_jacobi(phi, tr, noise) if jacobi else None
+                alpha, alpha_iters = self.cg_solve(phi, y[:, None].contiguous(), noise, tr, phi_t, tolerance, max_iter,
+                                                   precond=dinv)
             alpha = alpha.flatten()
         if info is not None:
             info["alpha_iterations"] = alpha_iters
@@ -1777,9 +1913,9 @@ class GRFEngine:
         def solve(Bv, c0, c1):
             if n:
                 if poly:
-                    X, it = self.cg_solve_poly(phi, f, Bv, noise, tr, tolerance, max_iter)
+                    X, it = self.cg_solve_poly(phi, f, Bv, noise, tr, tolerance, max_iter, precond=dinv)
                 else:
-                    X, it = self.cg_solve(phi, Bv, noise, tr, phi_t, tolerance, max_iter)
+                    X, it = self.cg_solve(phi, Bv, noise, tr, phi_t, tolerance, max_iter, precond=dinv)
             else:
                 X, it = Bv, 0
             iters.append(it)

@@ -312,10 +312,11 @@ class GRFMarginalLikelihoodFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, f: torch.Tensor, noise: torch.Tensor, steps, train_idx, y, probes,
-                tolerance: float, max_iter: int, info: Optional[dict]):
+                tolerance: float, max_iter: int, info: Optional[dict], preconditioner=None):
         eng = steps.engine
         value, g_f, g_noise, iters = eng.marginal_log_likelihood(
-            steps, f, train_idx, y, float(noise.detach().reshape(-1)[0].item()), probes, tolerance, max_iter)
+            steps, f, train_idx, y, float(noise.detach().reshape(-1)[0].item()), probes, tolerance, max_iter,
+            preconditioner=preconditioner)
         grad_f = torch.zeros(f.numel(), dtype=torch.float64, device=eng.device)
         grad_f[:g_f.numel()] = g_f  # (modulator entries past the last step matrix do not enter Phi)
         ctx.grad_f = grad_f.reshape(f.shape).to(device=f.device, dtype=f.dtype)
@@ -328,7 +329,7 @@ class GRFMarginalLikelihoodFunction(torch.autograd.Function):
     def backward(ctx, g: torch.Tensor):
         gf = ctx.grad_f * g.to(device=ctx.grad_f.device, dtype=ctx.grad_f.dtype)
         gn = ctx.grad_noise * g.to(device=ctx.grad_noise.device, dtype=ctx.grad_noise.dtype)
-        return gf, gn, None, None, None, None, None, None, None
+        return gf, gn, None, None, None, None, None, None, None, None
 
 
 def resolve_cg_tolerance(tolerance: Optional[float]) -> float:
@@ -346,7 +347,7 @@ def resolve_cg_tolerance(tolerance: Optional[float]) -> float:
 def grf_marginal_log_likelihood(f: torch.Tensor, noise, steps, train_idx, y, probes=None,
                                 n_probes: int = 64, generator=None, tolerance: Optional[float] = None,
                                 max_iter: int = 1000, per_datum: bool = True,
-                                info: Optional[dict] = None) -> torch.Tensor:
+                                info: Optional[dict] = None, preconditioner=None) -> torch.Tensor:
     """MLL(f, noise) of y at the training nodes, a differentiable fp64 scalar (on f's device).  steps: a
     StepMatrices (Phi = sum_l f_l M_l) or a WalkPolynomial (Phi = sum_l f_l G^l, matrix-free).
 
@@ -354,8 +355,14 @@ def grf_marginal_log_likelihood(f: torch.Tensor, noise, steps, train_idx, y, pro
     whatever they were computed from.  probes: (n_train x t) Hutchinson probes, t <= 255; by default
     ``torch.randn(n_train, n_probes, generator=generator)`` drawn on the generator's device, or on the
     engine's when there is none (no host draw and upload per training step).  per_datum divides by n_train,
-    as gpytorch's ExactMarginalLogLikelihood does.  info: a dict that receives ``cg_iterations``."""
+    as gpytorch's ExactMarginalLogLikelihood does.  info: a dict that receives ``cg_iterations``.
+    preconditioner: None, or "jacobi" -- the solve preconditioned by diag(K^), the probes rescaled so that the
+    value and the gradients estimate the same quantities (``GRFEngine.marginal_log_likelihood``); typically
+    several times fewer CG iterations on the walk estimator's Phi."""
     eng = steps.engine
+    if preconditioner is not None and preconditioner != "jacobi":
+        raise ValueError(f"grf_marginal_log_likelihood: preconditioner must be None or \"jacobi\", not "
+                         f"{preconditioner!r}")
     idx = torch.as_tensor(train_idx).flatten()
     n = idx.numel()
     yt = torch.as_tensor(y).flatten()
@@ -375,7 +382,7 @@ def grf_marginal_log_likelihood(f: torch.Tensor, noise, steps, train_idx, y, pro
     if noise.numel() != 1:
         raise ValueError("grf_marginal_log_likelihood: noise must have one element")
     out = GRFMarginalLikelihoodFunction.apply(f, noise, steps, idx, yt, probes, resolve_cg_tolerance(tolerance),
-                                              int(max_iter), info)
+                                              int(max_iter), info, preconditioner)
     return out / n if per_datum else out
 
 

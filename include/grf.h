@@ -72,7 +72,8 @@ enum grf_norm {
  * revision differs (argument lists, or -- ABI 7 -- the GRF_RNG_PHILOX stream, change between revisions;
  * ABI 8 added grf_phi_row_shifts_padded and grf_gram_sparse_cols_padded; ABI 9 the marginal likelihood's
  * grf_cg_gram_solve_lanczos_f64 and grf_steps_frob_f64; grf_spgemm_* and the record kinds' *_rec entries came
- * later, purely additive: no argument list of revision 9 changed, so the revision stays). */
+ * later, as did the diagonally preconditioned grf_pcg_* solves and grf_gram_jacobi_f64, purely additive: no
+ * argument list of revision 9 changed, so the revision stays). */
 #define GRF_ABI_VERSION 9
 
 const char *grf_last_error(void);
@@ -762,6 +763,59 @@ int32_t grf_cg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g
                                       int32_t n_rhs, double tolerance, int32_t max_iter, double *x, int64_t ldx,
                                       void *workspace, size_t workspace_bytes, int32_t *iters_out, double *resid_out,
                                       double *coef, int64_t ld_coef, grf_stream_t stream);
+
+/* ------------------------------------------- diagonally preconditioned solves (fp64; purely additive to ABI 9)
+ * linear_cg with a `preconditioner` closure z = dinv . r, dinv (device, n_sys doubles, all positive) the inverse
+ * of a diagonal D -- for D = diag(K^) the Jacobi preconditioner, which suits the walk estimator: its rows differ
+ * by orders of magnitude in norm and are nearly orthogonal once scaled, so D^-1/2 K^ D^-1/2 is close to I.
+ *     init:  r = b / ||b||, p = z = dinv . r, x = 0, rz = sum r.z
+ *     step:  alpha = rz / p.Ap (0 where p.Ap < eps or the column has converged); r -= alpha Ap; x += alpha p;
+ *            z = dinv . r; beta = rz_new / rz_old (0 where rz_old < eps); p = z + beta p.
+ * The residual norm behind has_converged, resid_out and the stopping rule stays the unpreconditioned ||r||; eps,
+ * stop_updating_after, the zero-rhs mask, the polling and the result * ||b|| write-out are those of
+ * grf_cg_gram_solve_f64.  z is never stored (formed where it is used); the init and update reductions carry two
+ * sums per column (r.z and r.r) in the plain solve's fixed order, so two calls give the same bits, and dinv = 1
+ * reproduces grf_cg_gram_solve_f64 / grf_cg_poly_solve_f64 bit for bit (x, iterations, residuals, coefficients).
+ * The _lanczos variants record alpha_k and beta_k as the plain ones do: they are the Lanczos coefficients of
+ * D^-1/2 K^ D^-1/2 started at D^1/2 b / ||.||.  Arguments: those of the unpreconditioned function, then dinv
+ * before the stream.  Workspaces: grf_pcg_workspace_bytes / grf_pcg_poly_workspace_bytes (larger than the plain
+ * ones by the second partial sums).
+ *
+ * grf_gram_jacobi_f64: dinv[r] = 1 / (sum_e Phi[row_map[r], e]^2 + noise), r < n_sel (row_map int32 or NULL; idx
+ * is not read).  Order rule: the squares (fp32 widened: exact in fp64) are added to +0.0 one by one in the row's
+ * stored order, then the noise, then one IEEE division.  Where the sum plus noise is not positive (an empty row
+ * with zero noise) dinv[r] = 1: the row is not preconditioned.  noise >= 0; n_sel == 0 touches nothing. */
+int32_t grf_gram_jacobi_f64(int64_t n_sel, const int64_t *ptr, const int32_t *idx, const float *val,
+                            const int32_t *row_map, double noise, double *dinv, grf_stream_t stream);
+size_t grf_pcg_workspace_bytes(int64_t n_sys, int64_t n_cols, int32_t n_rhs);
+int32_t grf_pcg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                               const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
+                               const float *t_val, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
+                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
+                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
+                               grf_stream_t stream);
+int32_t grf_pcg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                                       const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr,
+                                       const int32_t *t_idx, const float *t_val, double noise, const double *rhs,
+                                       int64_t ld_rhs, int32_t n_rhs, double tolerance, int32_t max_iter, double *x,
+                                       int64_t ldx, void *workspace, size_t workspace_bytes, int32_t *iters_out,
+                                       double *resid_out, double *coef, int64_t ld_coef, const double *dinv,
+                                       grf_stream_t stream);
+size_t grf_pcg_poly_workspace_bytes(int64_t n_sys, int64_t n, int32_t n_rhs);
+int32_t grf_pcg_poly_solve_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                               const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
+                               const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
+                               const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
+                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
+                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
+                               grf_stream_t stream);
+int32_t grf_pcg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                                       const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
+                                       const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
+                                       const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs,
+                                       int32_t n_rhs, double tolerance, int32_t max_iter, double *x, int64_t ldx,
+                                       void *workspace, size_t workspace_bytes, int32_t *iters_out, double *resid_out,
+                                       double *coef, int64_t ld_coef, const double *dinv, grf_stream_t stream);
 
 /* The modulator gradient's contraction on the operator (the training step of models/sparse_grf_model.py:21-45's
  * model; A, B, wt as in grf_steps_frob_f64): with a~ = S_T^T A, b~ = S_T^T B, W_A = p(G^T) a~, W_B = p(G^T) b~,
