@@ -1,4 +1,4 @@
-// grf_block.h -- wave64 / workgroup primitives (scan, bitonic sort) for gfx950.
+// grf_block.h -- wave64 / workgroup primitives (scan, bitonic sort, last-block ticket) for gfx950.
 #pragma once
 #include "grf_common.h"
 
@@ -86,6 +86,25 @@ __device__ inline T block_exclusive_scan_fast(T v, T *scratch, T *total) {
     }
     *total = all;
     return before + inc - v;
+}
+
+// The "last block, by ticket" hand-off of the deterministic reductions: every block of a launch writes its
+// partials to global memory, then the whole block calls this; true in the one block that drew the last of
+// the n_blocks tickets, which may then read every block's partials (and resets *ticket when it is done).
+//   fence 1 (release): each thread's partial stores are visible device-wide before its block's ticket is drawn;
+//   barrier 1:         every thread of the block has passed fence 1 before thread 0 draws the ticket;
+//   barrier 2:         the drawn result (an LDS flag of the helper's own) reaches the whole block;
+//   fence 2 (acquire): the last block's loads of the other blocks' partials are not served ahead of its ticket.
+// Contains barriers: all threads of the block must call it, once per launch.
+__device__ inline bool block_is_last(uint32_t *ticket, unsigned n_blocks) {
+    __shared__ uint32_t last;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == n_blocks - 1;
+    __syncthreads();
+    if (!last) return false;
+    __threadfence();
+    return true;
 }
 
 // In-LDS bitonic sort (ascending) of P = power-of-two 32- or 64-bit keys by the whole

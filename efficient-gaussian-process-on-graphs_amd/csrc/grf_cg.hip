@@ -18,9 +18,11 @@
 //   spmm_kernel<SG>             Y = A[row_map] X (+ zc Z); one wave per row, 64/SG
 //                               lane groups split the nonzeros, fixed-order sums.
 //   cg_* kernels                column reductions (fp64, fixed order, last block
-//                               finalises) and the vector updates of linear_cg.
-// The recurrence (cg_solve_impl) takes its matvec as a functor: GramMatVec is the two SpMMs above, PolyMatVec
-// the two Horner chains of the walk polynomial (grf_poly.hip: K = S_T p(G) p(G)^T S_T^T, no Phi formed).
+//                               finalises: block_is_last, grf_block.h) and the vector updates of linear_cg.
+// Host side: one recurrence (cg_solve_impl, templated on its matvec functor and on kPre) and one solve per operator:
+// cg_gram_solve on GramMatVec, the two SpMMs above, and cg_poly_solve on PolyMatVec, the two Horner chains of the walk
+// polynomial (grf_poly.hip: K = S_T p(G) p(G)^T S_T^T, no Phi formed).  A solve adds its operator's checks, layout and
+// functor; what the nine entry points share travels in a CgCall that names the entry and its variant.
 // kPre = true is the same recurrence with linear_cg's preconditioner closure z = dinv . r for a diagonal (grf_pcg_*):
 // z is formed in the reductions and in cg_dir_kernel, never stored; gram_jacobi_kernel makes dinv = 1 / diag(K^).
 // All CG kernels read a device `done` flag first: once the stopping rule fires
@@ -32,15 +34,13 @@
 
 #include <algorithm>
 
-#include "grf_common.h"
+#include "grf_block.h"
 #include "grf_poly.h"
 
 namespace grf {
 
 int32_t scan_counts_i32(int64_t n, const int32_t *cnt, int64_t *out, void *ws, size_t ws_bytes, hipStream_t st);
 size_t scan_ws_bytes(int64_t n);
-
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ------------------------------------------------------------ CSR transpose
 // (Phi[row_map])^T by a stable radix sort: the selected rows' entries are laid out in row order as
@@ -417,7 +417,6 @@ __global__ __launch_bounds__(256) void cg_reduce_kernel(int64_t n, int32_t S, T 
     __shared__ double red[4 * kSums][kMaxRhs];  // (sum j of wave w: red[4 * j + w])
     __shared__ double fin_norm[kMaxRhs];
     __shared__ int fin_conv[kMaxRhs];
-    __shared__ uint32_t last;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double acc[4] = {0.0, 0.0, 0.0, 0.0}, acc2[4] = {0.0, 0.0, 0.0, 0.0};
     const int64_t n_waves = (int64_t)gridDim.x * 4;
@@ -442,12 +441,7 @@ __global__ __launch_bounds__(256) void cg_reduce_kernel(int64_t n, int32_t S, T 
             st.part[((int64_t)j * kRedBlocks + blockIdx.x) * S + c] =
                 ((red[4 * j][c] + red[4 * j + 1][c]) + red[4 * j + 2][c]) + red[4 * j + 3][c];
     }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(st.ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!block_is_last(st.ticket, gridDim.x)) return;
     // the last block: column c summed over blocks in order; tpc threads per column split the
     // blocks into contiguous ranges, combined in range order
     const int tpc = max(1, 256 / S);
@@ -527,25 +521,32 @@ struct CgBase {
     size_t R, P, Y, X, part, dbl, i32;
 };
 
+// R P Y X | `mid` bytes of the operator's own, from *mid_off | part dbl i32; returns the end
+// (n_sums = 2: the preconditioned variant's two partials per (block, column))
+static size_t cg_base_layout(CgBase &b, size_t *mid_off, int64_t n_sys, int32_t S, size_t elem, size_t mid,
+                             int n_sums) {
+    size_t o = 0;
+    const size_t vec = al256((size_t)n_sys * S * elem);
+    b.R = o; o += vec;
+    b.P = o; o += vec;
+    b.Y = o; o += vec;
+    b.X = o; o += vec;
+    *mid_off = o; o += mid;
+    b.part = o; o += al256((size_t)n_sums * kRedBlocks * S * sizeof(double));
+    b.dbl = o; o += al256((size_t)5 * S * sizeof(double));
+    b.i32 = o; o += al256((size_t)(2 * S + 8) * sizeof(int32_t));
+    return o;
+}
+
 struct CgLayout {
     CgBase base;
     size_t W, seg1, seg2, total;
     int32_t tw1, nt1, tw2, nt2;  // column tiles of Phi_t^T (over the n_sys rows of P) and Phi_t (over W)
 };
 
-// (n_sums = 2: the preconditioned variant's two partials per (block, column))
-static CgLayout cg_layout(int64_t n_sys, int64_t n_cols, int32_t S, size_t elem, int n_sums = 1) {
+static CgLayout cg_layout(int64_t n_sys, int64_t n_cols, int32_t S, size_t elem, int n_sums) {
     CgLayout l{};
-    size_t o = 0;
-    const size_t vec = al256((size_t)n_sys * S * elem);
-    l.base.R = o; o += vec;
-    l.base.P = o; o += vec;
-    l.base.Y = o; o += vec;
-    l.base.X = o; o += vec;
-    l.W = o; o += al256((size_t)n_cols * S * elem);
-    l.base.part = o; o += al256((size_t)n_sums * kRedBlocks * S * sizeof(double));
-    l.base.dbl = o; o += al256((size_t)5 * S * sizeof(double));
-    l.base.i32 = o; o += al256((size_t)(2 * S + 8) * sizeof(int32_t));
+    size_t o = cg_base_layout(l.base, &l.W, n_sys, S, elem, al256((size_t)n_cols * S * elem), n_sums);
     l.tw1 = spmm_tile_rows(n_sys, S, elem);
     l.nt1 = l.tw1 ? (int32_t)cdiv<int64_t>(n_sys, l.tw1) : 1;
     l.tw2 = spmm_tile_rows(n_cols, S, elem);
@@ -598,21 +599,12 @@ struct CgPolyLayout {
     size_t W, H0, H1, total;
 };
 
-static CgPolyLayout cg_poly_layout(int64_t n_sys, int64_t n, int32_t S, int n_sums = 1) {
+static CgPolyLayout cg_poly_layout(int64_t n_sys, int64_t n, int32_t S, int n_sums) {
     CgPolyLayout l{};
-    size_t o = 0;
-    const size_t vec = al256((size_t)n_sys * S * sizeof(double)), blk = al256((size_t)n * S * sizeof(double));
-    l.base.R = o; o += vec;
-    l.base.P = o; o += vec;
-    l.base.Y = o; o += vec;
-    l.base.X = o; o += vec;
-    l.W = o; o += blk;
-    l.H0 = o; o += blk;
-    l.H1 = o; o += blk;
-    l.base.part = o; o += al256((size_t)n_sums * kRedBlocks * S * sizeof(double));
-    l.base.dbl = o; o += al256((size_t)5 * S * sizeof(double));
-    l.base.i32 = o; o += al256((size_t)(2 * S + 8) * sizeof(int32_t));
-    l.total = o;
+    const size_t blk = al256((size_t)n * S * sizeof(double));
+    l.total = cg_base_layout(l.base, &l.W, n_sys, S, sizeof(double), 3 * blk, n_sums);
+    l.H0 = l.W + blk;
+    l.H1 = l.H0 + blk;
     return l;
 }
 
@@ -640,18 +632,68 @@ struct PolyMatVec {
     }
 };
 
+// What an entry asks of the recurrence: `who` is its name (every message carries it), `pre` / `lanczos` its variant,
+// stated by the entry and never inferred from a NULL dinv or coef, which are argument errors of those variants.
+template <typename T>
+struct CgCall {
+    const char *who;
+    bool pre, lanczos;
+    const T *rhs; int64_t ld_rhs; int32_t n_rhs;
+    double tolerance; int32_t max_iter;
+    T *x; int64_t ldx;
+    void *workspace; size_t workspace_bytes;
+    int32_t *iters_out; double *resid_out;
+    grf_stream_t stream;
+    double *coef = nullptr; int64_t ld_coef = 0;   // the Lanczos entries'
+    const double *dinv = nullptr;                  // the preconditioned entries'
+};
+
+// the checks every solve shares (the operator's own come before, the workspace size after the layout)
+template <typename T>
+static int32_t cg_check_call(const CgCall<T> &c) {
+    GRF_REQUIRE(!c.lanczos || (c.coef && c.ld_coef >= c.n_rhs), GRF_EINVAL, "%s: bad coefficient buffer", c.who);
+    GRF_REQUIRE(c.rhs && c.x && (!c.pre || c.dinv), GRF_EINVAL, "%s: bad arguments", c.who);
+    GRF_REQUIRE(c.n_rhs >= 1 && c.n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "%s: n_rhs must be in [1, %d]", c.who, kMaxRhs);
+    GRF_REQUIRE(c.ld_rhs >= c.n_rhs && c.ldx >= c.n_rhs && c.max_iter >= 0, GRF_EINVAL, "%s: bad strides", c.who);
+    return GRF_OK;
+}
+
+// One solve's pinned words ([done of even iterations, done of odd iterations, iters]) and events.  On every return
+// path the stream is synchronised (unless the solve just did: a copy into the words may be in flight), then all freed.
+struct CgPoll {
+    hipStream_t sm;
+    int32_t *h = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool synced = false;
+
+    hipError_t sync() {
+        synced = true;
+        return hipStreamSynchronize(sm);
+    }
+    int32_t init() {
+        GRF_CHECK_HIP(hipHostMalloc((void **)&h, 4 * sizeof(int32_t), hipHostMallocDefault));
+        GRF_CHECK_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
+        GRF_CHECK_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+        return GRF_OK;
+    }
+    ~CgPoll() {
+        if (!synced) (void)sync();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (h) (void)hipHostFree(h);
+    }
+};
+
 // linear_cg on n_sys x n_rhs systems; `mv` computes Y = (K + s2 I) P on the stream (the checks of its own
 // operands are the caller's); `l`: where the recurrence's buffers lie in the workspace.  kPre: linear_cg with
 // the preconditioner closure z = dinv . r (p = z + beta p, alpha and beta from r.z, the norms from r.r)
-template <typename T, bool kPre = false, typename MatVec>
-static int32_t cg_solve_impl(int64_t n_sys, MatVec &mv, const CgBase &l, const T *rhs, int64_t ld_rhs, int32_t n_rhs,
-                             double tolerance, int32_t max_iter, T *x, int64_t ldx, void *workspace,
-                             int32_t *iters_out, double *resid_out, grf_stream_t stream, double *coef = nullptr,
-                             int64_t ld_coef = 0, const double *dinv = nullptr) {
-    hipStream_t sm = S(stream);
-    char *w = (char *)workspace;
+template <typename T, bool kPre, typename MatVec>
+static int32_t cg_solve_impl(int64_t n_sys, MatVec &mv, const CgBase &l, const CgCall<T> &c) {
+    hipStream_t sm = S(c.stream);
+    char *w = (char *)c.workspace;
     T *R = (T *)(w + l.R), *P = (T *)(w + l.P), *Y = (T *)(w + l.Y), *X = (T *)(w + l.X);
-    const int32_t Sn = n_rhs;
+    const int32_t Sn = c.n_rhs, max_iter = c.max_iter;
+    const double tolerance = c.tolerance, *dinv = c.dinv;
     CgState st;
     double *d = (double *)(w + l.dbl);
     st.rhs_norm = d; st.rr = d + Sn; st.alpha = d + 2 * Sn; st.beta = d + 3 * Sn; st.rnorm = d + 4 * Sn;
@@ -660,52 +702,49 @@ static int32_t cg_solve_impl(int64_t n_sys, MatVec &mv, const CgBase &l, const T
     st.rhs_zero = q; st.conv = q + Sn;
     st.ticket = (uint32_t *)(q + 2 * Sn); st.iters = q + 2 * Sn + 1; st.done = q + 2 * Sn + 2;
     GRF_CHECK_HIP(hipMemsetAsync(q, 0, (size_t)(2 * Sn + 8) * sizeof(int32_t), sm));
-    st.coef = coef; st.ld_coef = ld_coef; st.max_iter = max_iter;
-    if (coef && max_iter > 0)
-        GRF_CHECK_HIP(hipMemsetAsync(coef, 0, (size_t)2 * max_iter * ld_coef * sizeof(double), sm));
+    st.coef = c.coef; st.ld_coef = c.ld_coef; st.max_iter = max_iter;
+    if (c.coef && max_iter > 0)
+        GRF_CHECK_HIP(hipMemsetAsync(c.coef, 0, (size_t)2 * max_iter * c.ld_coef * sizeof(double), sm));
 
     const unsigned rb = (unsigned)std::min<int64_t>(cdiv<int64_t>(n_sys, 4), kRedBlocks);
     const int64_t nel = n_sys * Sn;
     GRF_REQUIRE_GRID(cdiv<int64_t>(nel, 256), 256, "cg_dir_kernel");
     const unsigned eb = (unsigned)cdiv<int64_t>(nel, 256);
     const int32_t k_check = std::min(10, max_iter - 1);
-    int32_t rc0;
+    int32_t rc;
 
-    if ((rc0 = mv.prepare(w, sm)) != GRF_OK) return rc0;
-    cg_reduce_kernel<kFinNorm, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance, dinv);
+    if ((rc = mv.prepare(w, sm)) != GRF_OK) return rc;
+    cg_reduce_kernel<kFinNorm, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, c.rhs, c.ld_rhs, st, k_check, tolerance, dinv);
     GRF_CHECK_LAUNCH("cg_reduce_kernel<norm>");
-    cg_reduce_kernel<kFinInit, T, kPre><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance, dinv);
+    cg_reduce_kernel<kFinInit, T, kPre><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, c.rhs, c.ld_rhs, st, k_check, tolerance, dinv);
     GRF_CHECK_LAUNCH("cg_reduce_kernel<init>");
 
-    int32_t *h = nullptr;  // pinned: [done of even iterations, done of odd iterations, iters]
-    GRF_CHECK_HIP(hipHostMalloc((void **)&h, 4 * sizeof(int32_t), hipHostMallocDefault));
-    hipEvent_t ev[2];
-    GRF_CHECK_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-    GRF_CHECK_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
-    int32_t rc = GRF_OK;
+    CgPoll poll{sm};
+    if ((rc = poll.init()) != GRF_OK) return rc;
+    int32_t *h = poll.h;
     for (int32_t k = 0; k < max_iter && rc == GRF_OK; ++k) {
         // mvms = (K + s2 I) p
         rc = mv(P, Y, Sn, st.done, sm);
         if (rc != GRF_OK) break;
-        cg_reduce_kernel<kFinAlpha, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance, dinv);
-        cg_reduce_kernel<kFinUpdate, T, kPre><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, rhs, ld_rhs, st, k_check, tolerance, dinv);
+        cg_reduce_kernel<kFinAlpha, T><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, c.rhs, c.ld_rhs, st, k_check, tolerance, dinv);
+        cg_reduce_kernel<kFinUpdate, T, kPre><<<rb, 256, 0, sm>>>(n_sys, Sn, R, P, Y, X, c.rhs, c.ld_rhs, st, k_check, tolerance, dinv);
         cg_dir_kernel<T, kPre><<<eb, 256, 0, sm>>>(n_sys, Sn, R, P, st, dinv);
         if (hipGetLastError() != hipSuccess) {
-            set_error("grf_cg_gram_solve: launch failed");
+            set_error("%s: launch failed", c.who);
             rc = GRF_EHIP;
             break;
         }
         if (k < k_check) continue;
         // poll: copy this iteration's flag, then look at the previous one's (one iteration in flight)
         if (hipMemcpyAsync(&h[k & 1], st.done, sizeof(int32_t), hipMemcpyDeviceToHost, sm) != hipSuccess ||
-            hipEventRecord(ev[k & 1], sm) != hipSuccess) {
-            set_error("grf_cg_gram_solve: poll failed");
+            hipEventRecord(poll.ev[k & 1], sm) != hipSuccess) {
+            set_error("%s: poll failed", c.who);
             rc = GRF_EHIP;
             break;
         }
         if (k > k_check) {
-            if (hipEventSynchronize(ev[(k - 1) & 1]) != hipSuccess) {
-                set_error("grf_cg_gram_solve: event wait failed");
+            if (hipEventSynchronize(poll.ev[(k - 1) & 1]) != hipSuccess) {
+                set_error("%s: event wait failed", c.who);
                 rc = GRF_EHIP;
                 break;
             }
@@ -713,75 +752,65 @@ static int32_t cg_solve_impl(int64_t n_sys, MatVec &mv, const CgBase &l, const T
         }
     }
     if (rc == GRF_OK) {
-        cg_out_kernel<T><<<eb, 256, 0, sm>>>(n_sys, Sn, X, x, ldx, st);
+        cg_out_kernel<T><<<eb, 256, 0, sm>>>(n_sys, Sn, X, c.x, c.ldx, st);
         if (hipGetLastError() != hipSuccess) {
-            set_error("grf_cg_gram_solve: launch of cg_out_kernel failed");
+            set_error("%s: launch of cg_out_kernel failed", c.who);
             rc = GRF_EHIP;
         }
     }
-    if (rc == GRF_OK && (iters_out || resid_out)) {
+    if (rc == GRF_OK && (c.iters_out || c.resid_out)) {
         if (hipMemcpyAsync(&h[2], st.iters, sizeof(int32_t), hipMemcpyDeviceToHost, sm) != hipSuccess ||
-            (resid_out && hipMemcpyAsync(resid_out, st.rnorm, Sn * sizeof(double), hipMemcpyDeviceToHost, sm) !=
-                              hipSuccess) ||
-            hipStreamSynchronize(sm) != hipSuccess) {
-            set_error("grf_cg_gram_solve: reading the iteration count failed");
+            (c.resid_out && hipMemcpyAsync(c.resid_out, st.rnorm, Sn * sizeof(double), hipMemcpyDeviceToHost, sm) !=
+                                hipSuccess) ||
+            poll.sync() != hipSuccess) {
+            set_error("%s: reading the iteration count failed", c.who);
             rc = GRF_EHIP;
-        } else {
-            if (iters_out) *iters_out = h[2];
+        } else if (c.iters_out) {
+            *c.iters_out = h[2];
         }
-    } else {
-        (void)hipStreamSynchronize(sm);  // the pinned buffer is freed below
     }
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-    (void)hipHostFree(h);
     return rc;
+}
+
+// the workspace check, then the recurrence of the variant the entry named (kPre exists in fp64 only)
+template <typename T, typename MatVec>
+static int32_t cg_run(int64_t n_sys, MatVec &mv, const CgBase &l, size_t total, const CgCall<T> &c) {
+    GRF_REQUIRE(c.workspace && c.workspace_bytes >= total, GRF_EINVAL, "%s: workspace too small (%zu < %zu)", c.who,
+                c.workspace_bytes, total);
+    if constexpr (sizeof(T) == sizeof(double)) {
+        if (c.pre) return cg_solve_impl<T, true>(n_sys, mv, l, c);
+    }
+    return cg_solve_impl<T, false>(n_sys, mv, l, c);
 }
 
 // the Phi-based solve: its argument checks, then the shared recurrence on the two SpMMs
 template <typename T>
 static int32_t cg_gram_solve(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
                              const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
-                             const float *t_val, double noise, const T *rhs, int64_t ld_rhs, int32_t n_rhs,
-                             double tolerance, int32_t max_iter, T *x, int64_t ldx, void *workspace,
-                             size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream,
-                             double *coef = nullptr, int64_t ld_coef = 0) {
-    GRF_REQUIRE(n_sys > 0 && n_cols > 0 && ptr && t_ptr && rhs && x, GRF_EINVAL, "grf_cg_gram_solve: bad arguments");
-    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_cg_gram_solve: n_rhs must be in [1, %d]",
-                kMaxRhs);
-    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_cg_gram_solve: bad strides");
-    const CgLayout l = cg_layout(n_sys, n_cols, n_rhs, sizeof(T));
-    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL, "grf_cg_gram_solve: workspace too small (%zu < %zu)",
-                workspace_bytes, l.total);
+                             const float *t_val, double noise, const CgCall<T> &c) {
+    GRF_REQUIRE(n_sys > 0 && n_cols > 0 && ptr && t_ptr, GRF_EINVAL, "%s: bad arguments", c.who);
+    if (const int32_t rc = cg_check_call(c); rc != GRF_OK) return rc;
+    const CgLayout l = cg_layout(n_sys, n_cols, c.n_rhs, sizeof(T), c.pre ? 2 : 1);
     GramMatVec<T> mv{n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, l};
-    return cg_solve_impl<T>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, iters_out,
-                            resid_out, stream, coef, ld_coef);
+    return cg_run(n_sys, mv, l.base, l.total, c);
 }
 
 // the same recurrence on the walk polynomial (fp64 only)
 static int32_t cg_poly_solve(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
                              const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
                              const double *f, int32_t n_f, const int32_t *row_map, const int32_t *inv_map,
-                             double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs, double tolerance,
-                             int32_t max_iter, double *x, int64_t ldx, void *workspace, size_t workspace_bytes,
-                             int32_t *iters_out, double *resid_out, grf_stream_t stream, double *coef = nullptr,
-                             int64_t ld_coef = 0) {
-    GRF_REQUIRE(n_sys > 0 && n > 0 && g_ptr && gt_ptr && f && n_f >= 1 && row_map && inv_map && rhs && x, GRF_EINVAL,
-                "grf_cg_poly_solve: bad arguments");
-    GRF_REQUIRE(n < (1ll << 31) && n_sys < (1ll << 31), GRF_EUNSUPPORTED, "grf_cg_poly_solve: more than 2^31 rows");
-    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_cg_poly_solve: n_rhs must be in [1, %d]",
-                kMaxRhs);
-    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_cg_poly_solve: bad strides");
-    const CgPolyLayout l = cg_poly_layout(n_sys, n, n_rhs);
-    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL, "grf_cg_poly_solve: workspace too small (%zu < %zu)",
-                workspace_bytes, l.total);
+                             double noise, const CgCall<double> &c) {
+    GRF_REQUIRE(n_sys > 0 && n > 0 && g_ptr && gt_ptr && f && n_f >= 1 && row_map && inv_map, GRF_EINVAL,
+                "%s: bad arguments", c.who);
+    GRF_REQUIRE(n < (1ll << 31) && n_sys < (1ll << 31), GRF_EUNSUPPORTED, "%s: more than 2^31 rows", c.who);
+    if (const int32_t rc = cg_check_call(c); rc != GRF_OK) return rc;
+    const CgPolyLayout l = cg_poly_layout(n_sys, n, c.n_rhs, c.pre ? 2 : 1);
     PolyMatVec mv{n_sys, PolyOp{n, g_ptr, g_idx, g_val, f, n_f}, PolyOp{n, gt_ptr, gt_idx, gt_val, f, n_f}, row_map,
                   inv_map, noise, l};
-    return cg_solve_impl<double>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace,
-                                 iters_out, resid_out, stream, coef, ld_coef);
+    return cg_run(n_sys, mv, l.base, l.total, c);
 }
 
-// ------------------------------------------------- the diagonally preconditioned solves (fp64 only)
+// ------------------------------------------------- the Jacobi preconditioner (fp64 only)
 // dinv[r] = 1 / (sum_e Phi[row_map[r], e]^2 + noise) = 1 / diag(K^)[r]: one wave per row; the squares (fp32
 // widened: exact in fp64) are added to +0.0 one by one in the row's stored order, every lane the same sum.
 // A row whose sum plus noise is not positive (empty, zero noise) gets 1: it is not preconditioned.
@@ -804,47 +833,6 @@ __global__ __launch_bounds__(256) void gram_jacobi_kernel(int64_t n_sel, const i
     }
     const double d = acc + noise;
     if (lane == 0) dinv[r] = d > 0.0 ? 1.0 / d : 1.0;
-}
-
-static int32_t pcg_gram_solve(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
-                              const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
-                              const float *t_val, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
-                              double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
-                              size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
-                              grf_stream_t stream, double *coef = nullptr, int64_t ld_coef = 0) {
-    GRF_REQUIRE(n_sys > 0 && n_cols > 0 && ptr && t_ptr && rhs && x && dinv, GRF_EINVAL,
-                "grf_pcg_gram_solve: bad arguments");
-    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_pcg_gram_solve: n_rhs must be in [1, %d]",
-                kMaxRhs);
-    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_pcg_gram_solve: bad strides");
-    const CgLayout l = cg_layout(n_sys, n_cols, n_rhs, sizeof(double), 2);
-    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL,
-                "grf_pcg_gram_solve: workspace too small (%zu < %zu)", workspace_bytes, l.total);
-    GramMatVec<double> mv{n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, l};
-    return cg_solve_impl<double, true>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace,
-                                       iters_out, resid_out, stream, coef, ld_coef, dinv);
-}
-
-static int32_t pcg_poly_solve(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
-                              const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx, const double *gt_val,
-                              const double *f, int32_t n_f, const int32_t *row_map, const int32_t *inv_map,
-                              double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs, double tolerance,
-                              int32_t max_iter, double *x, int64_t ldx, void *workspace, size_t workspace_bytes,
-                              int32_t *iters_out, double *resid_out, const double *dinv, grf_stream_t stream,
-                              double *coef = nullptr, int64_t ld_coef = 0) {
-    GRF_REQUIRE(n_sys > 0 && n > 0 && g_ptr && gt_ptr && f && n_f >= 1 && row_map && inv_map && rhs && x && dinv,
-                GRF_EINVAL, "grf_pcg_poly_solve: bad arguments");
-    GRF_REQUIRE(n < (1ll << 31) && n_sys < (1ll << 31), GRF_EUNSUPPORTED, "grf_pcg_poly_solve: more than 2^31 rows");
-    GRF_REQUIRE(n_rhs >= 1 && n_rhs <= kMaxRhs, GRF_EUNSUPPORTED, "grf_pcg_poly_solve: n_rhs must be in [1, %d]",
-                kMaxRhs);
-    GRF_REQUIRE(ld_rhs >= n_rhs && ldx >= n_rhs && max_iter >= 0, GRF_EINVAL, "grf_pcg_poly_solve: bad strides");
-    const CgPolyLayout l = cg_poly_layout(n_sys, n, n_rhs, 2);
-    GRF_REQUIRE(workspace && workspace_bytes >= l.total, GRF_EINVAL,
-                "grf_pcg_poly_solve: workspace too small (%zu < %zu)", workspace_bytes, l.total);
-    PolyMatVec mv{n_sys, PolyOp{n, g_ptr, g_idx, g_val, f, n_f}, PolyOp{n, gt_ptr, gt_idx, gt_val, f, n_f}, row_map,
-                  inv_map, noise, l};
-    return cg_solve_impl<double, true>(n_sys, mv, l.base, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace,
-                                       iters_out, resid_out, stream, coef, ld_coef, dinv);
 }
 
 }  // namespace grf
@@ -928,17 +916,32 @@ int32_t grf_spmm_csr_f64(int64_t n_out, const int64_t *ptr, const int32_t *idx, 
 }
 
 size_t grf_cg_workspace_bytes(int64_t n_sys, int64_t n_cols, int32_t n_rhs) {
-    return std::max(cg_layout(n_sys, n_cols, n_rhs, sizeof(float)).total,
-                    cg_layout(n_sys, n_cols, n_rhs, sizeof(double)).total);
+    return std::max(cg_layout(n_sys, n_cols, n_rhs, sizeof(float), 1).total,
+                    cg_layout(n_sys, n_cols, n_rhs, sizeof(double), 1).total);
 }
 
+size_t grf_pcg_workspace_bytes(int64_t n_sys, int64_t n_cols, int32_t n_rhs) {
+    return cg_layout(n_sys, n_cols, n_rhs, sizeof(double), 2).total;
+}
+
+size_t grf_cg_poly_workspace_bytes(int64_t n_sys, int64_t n, int32_t n_rhs) {
+    return cg_poly_layout(n_sys, n, n_rhs, 1).total;
+}
+
+size_t grf_pcg_poly_workspace_bytes(int64_t n_sys, int64_t n, int32_t n_rhs) {
+    return cg_poly_layout(n_sys, n, n_rhs, 2).total;
+}
+
+// The nine solves: each forwards its operator's arguments and a CgCall {its name, preconditioned?, Lanczos?,
+// the recurrence's arguments in the order of the signature [, coef, ld_coef [, dinv]]}.
 int32_t grf_cg_gram_solve(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
                           const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
                           const float *t_val, double noise, const float *rhs, int64_t ld_rhs, int32_t n_rhs,
                           double tolerance, int32_t max_iter, float *x, int64_t ldx, void *workspace,
                           size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream) {
-    return cg_gram_solve<float>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs, n_rhs,
-                                tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out, stream);
+    return cg_gram_solve<float>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise,
+                                {"grf_cg_gram_solve", false, false, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx,
+                                 workspace, workspace_bytes, iters_out, resid_out, stream});
 }
 
 int32_t grf_cg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
@@ -946,9 +949,9 @@ int32_t grf_cg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *
                               const float *t_val, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, grf_stream_t stream) {
-    return cg_gram_solve<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs,
-                                 n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
-                                 stream);
+    return cg_gram_solve<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise,
+                                 {"grf_cg_gram_solve_f64", false, false, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx,
+                                  workspace, workspace_bytes, iters_out, resid_out, stream});
 }
 
 int32_t grf_cg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
@@ -957,14 +960,33 @@ int32_t grf_cg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const i
                                       int64_t ld_rhs, int32_t n_rhs, double tolerance, int32_t max_iter, double *x,
                                       int64_t ldx, void *workspace, size_t workspace_bytes, int32_t *iters_out,
                                       double *resid_out, double *coef, int64_t ld_coef, grf_stream_t stream) {
-    GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_cg_gram_solve_lanczos_f64: bad coefficient buffer");
-    return cg_gram_solve<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs,
-                                 n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
-                                 stream, coef, ld_coef);
+    return cg_gram_solve<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise,
+                                 {"grf_cg_gram_solve_lanczos_f64", false, true, rhs, ld_rhs, n_rhs, tolerance, max_iter,
+                                  x, ldx, workspace, workspace_bytes, iters_out, resid_out, stream, coef, ld_coef});
 }
 
-size_t grf_cg_poly_workspace_bytes(int64_t n_sys, int64_t n, int32_t n_rhs) {
-    return cg_poly_layout(n_sys, n, n_rhs).total;
+int32_t grf_pcg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                               const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
+                               const float *t_val, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
+                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
+                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
+                               grf_stream_t stream) {
+    return cg_gram_solve<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise,
+                                 {"grf_pcg_gram_solve_f64", true, false, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx,
+                                  workspace, workspace_bytes, iters_out, resid_out, stream, nullptr, 0, dinv});
+}
+
+int32_t grf_pcg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
+                                       const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr,
+                                       const int32_t *t_idx, const float *t_val, double noise, const double *rhs,
+                                       int64_t ld_rhs, int32_t n_rhs, double tolerance, int32_t max_iter, double *x,
+                                       int64_t ldx, void *workspace, size_t workspace_bytes, int32_t *iters_out,
+                                       double *resid_out, double *coef, int64_t ld_coef, const double *dinv,
+                                       grf_stream_t stream) {
+    return cg_gram_solve<double>(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise,
+                                 {"grf_pcg_gram_solve_lanczos_f64", true, true, rhs, ld_rhs, n_rhs, tolerance, max_iter,
+                                  x, ldx, workspace, workspace_bytes, iters_out, resid_out, stream, coef, ld_coef,
+                                  dinv});
 }
 
 int32_t grf_cg_poly_solve_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
@@ -973,9 +995,9 @@ int32_t grf_cg_poly_solve_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, co
                               double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs, double tolerance,
                               int32_t max_iter, double *x, int64_t ldx, void *workspace, size_t workspace_bytes,
                               int32_t *iters_out, double *resid_out, grf_stream_t stream) {
-    return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
-                         ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
-                         stream);
+    return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise,
+                         {"grf_cg_poly_solve_f64", false, false, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx,
+                          workspace, workspace_bytes, iters_out, resid_out, stream});
 }
 
 int32_t grf_cg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
@@ -985,10 +1007,33 @@ int32_t grf_cg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g
                                       int32_t n_rhs, double tolerance, int32_t max_iter, double *x, int64_t ldx,
                                       void *workspace, size_t workspace_bytes, int32_t *iters_out, double *resid_out,
                                       double *coef, int64_t ld_coef, grf_stream_t stream) {
-    GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_cg_poly_solve_lanczos_f64: bad coefficient buffer");
-    return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
-                         ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
-                         stream, coef, ld_coef);
+    return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise,
+                         {"grf_cg_poly_solve_lanczos_f64", false, true, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx,
+                          workspace, workspace_bytes, iters_out, resid_out, stream, coef, ld_coef});
+}
+
+int32_t grf_pcg_poly_solve_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                               const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
+                               const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
+                               const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
+                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
+                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
+                               grf_stream_t stream) {
+    return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise,
+                         {"grf_pcg_poly_solve_f64", true, false, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx,
+                          workspace, workspace_bytes, iters_out, resid_out, stream, nullptr, 0, dinv});
+}
+
+int32_t grf_pcg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
+                                       const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
+                                       const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
+                                       const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs,
+                                       int32_t n_rhs, double tolerance, int32_t max_iter, double *x, int64_t ldx,
+                                       void *workspace, size_t workspace_bytes, int32_t *iters_out, double *resid_out,
+                                       double *coef, int64_t ld_coef, const double *dinv, grf_stream_t stream) {
+    return cg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise,
+                         {"grf_pcg_poly_solve_lanczos_f64", true, true, rhs, ld_rhs, n_rhs, tolerance, max_iter, x, ldx,
+                          workspace, workspace_bytes, iters_out, resid_out, stream, coef, ld_coef, dinv});
 }
 
 int32_t grf_gram_jacobi_f64(int64_t n_sel, const int64_t *ptr, const int32_t *idx, const float *val,
@@ -1001,62 +1046,6 @@ int32_t grf_gram_jacobi_f64(int64_t n_sel, const int64_t *ptr, const int32_t *id
     gram_jacobi_kernel<<<(unsigned)cdiv<int64_t>(n_sel, 4), 256, 0, S(stream)>>>(n_sel, ptr, val, row_map, noise, dinv);
     GRF_CHECK_LAUNCH("gram_jacobi_kernel");
     return GRF_OK;
-}
-
-size_t grf_pcg_workspace_bytes(int64_t n_sys, int64_t n_cols, int32_t n_rhs) {
-    return cg_layout(n_sys, n_cols, n_rhs, sizeof(double), 2).total;
-}
-
-int32_t grf_pcg_gram_solve_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
-                               const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
-                               const float *t_val, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
-                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
-                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
-                               grf_stream_t stream) {
-    return pcg_gram_solve(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs, n_rhs,
-                          tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out, dinv, stream);
-}
-
-int32_t grf_pcg_gram_solve_lanczos_f64(int64_t n_sys, const int64_t *ptr, const int32_t *idx, const float *val,
-                                       const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr,
-                                       const int32_t *t_idx, const float *t_val, double noise, const double *rhs,
-                                       int64_t ld_rhs, int32_t n_rhs, double tolerance, int32_t max_iter, double *x,
-                                       int64_t ldx, void *workspace, size_t workspace_bytes, int32_t *iters_out,
-                                       double *resid_out, double *coef, int64_t ld_coef, const double *dinv,
-                                       grf_stream_t stream) {
-    GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_pcg_gram_solve_lanczos_f64: bad coefficient buffer");
-    return pcg_gram_solve(n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, rhs, ld_rhs, n_rhs,
-                          tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out, dinv, stream,
-                          coef, ld_coef);
-}
-
-size_t grf_pcg_poly_workspace_bytes(int64_t n_sys, int64_t n, int32_t n_rhs) {
-    return cg_poly_layout(n_sys, n, n_rhs, 2).total;
-}
-
-int32_t grf_pcg_poly_solve_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
-                               const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
-                               const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
-                               const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs, int32_t n_rhs,
-                               double tolerance, int32_t max_iter, double *x, int64_t ldx, void *workspace,
-                               size_t workspace_bytes, int32_t *iters_out, double *resid_out, const double *dinv,
-                               grf_stream_t stream) {
-    return pcg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
-                          ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
-                          dinv, stream);
-}
-
-int32_t grf_pcg_poly_solve_lanczos_f64(int64_t n_sys, int64_t n, const int64_t *g_ptr, const int32_t *g_idx,
-                                       const double *g_val, const int64_t *gt_ptr, const int32_t *gt_idx,
-                                       const double *gt_val, const double *f, int32_t n_f, const int32_t *row_map,
-                                       const int32_t *inv_map, double noise, const double *rhs, int64_t ld_rhs,
-                                       int32_t n_rhs, double tolerance, int32_t max_iter, double *x, int64_t ldx,
-                                       void *workspace, size_t workspace_bytes, int32_t *iters_out, double *resid_out,
-                                       double *coef, int64_t ld_coef, const double *dinv, grf_stream_t stream) {
-    GRF_REQUIRE(coef && ld_coef >= n_rhs, GRF_EINVAL, "grf_pcg_poly_solve_lanczos_f64: bad coefficient buffer");
-    return pcg_poly_solve(n_sys, n, g_ptr, g_idx, g_val, gt_ptr, gt_idx, gt_val, f, n_f, row_map, inv_map, noise, rhs,
-                          ld_rhs, n_rhs, tolerance, max_iter, x, ldx, workspace, workspace_bytes, iters_out, resid_out,
-                          dinv, stream, coef, ld_coef);
 }
 
 #pragma GCC visibility pop

@@ -17,6 +17,9 @@ constexpr int kWave = 64;
 template <typename T>
 __host__ __device__ inline T cdiv(T a, T b) { return (a + b - 1) / b; }
 
+// workspace carving: every buffer starts on a 256-byte boundary
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 __host__ __device__ inline uint32_t next_pow2_u32(uint32_t v) {
     if (v <= 1) return 1;
     --v;

@@ -38,8 +38,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 enum GemmMode { kGeneral = 0, kSymmetric = 1, kContract = 2 };
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct GemmArgs {
     int64_t n1, n2, nk;
     const double *A;

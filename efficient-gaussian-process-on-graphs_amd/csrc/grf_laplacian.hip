@@ -892,7 +892,6 @@ __global__ __launch_bounds__(256) void lapd_emit_kernel(int64_t n, const double 
 
 // ------------------------------------------------------------------- host
 // The workspaces' byte offsets, each the one source of its size function and of the entry's pointers.
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // CSR: [row counts, n i32 | scan scratch]
 struct LapCsrWs {

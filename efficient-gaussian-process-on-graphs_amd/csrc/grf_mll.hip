@@ -18,7 +18,7 @@
 
 #include <algorithm>
 
-#include "grf_common.h"
+#include "grf_block.h"
 
 namespace grf {
 namespace {
@@ -33,8 +33,6 @@ struct FrobSteps {  // L <= 64 step matrices (device pointers), passed by value
     const float *val[kFrobMaxSteps];
 };
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 unsigned frob_row_blocks(int64_t n_sel) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv<int64_t>(n_sel, 4), kFrobBlocks));
 }
@@ -47,7 +45,6 @@ __global__ __launch_bounds__(256) void steps_frob_kernel(int64_t n_sel, int32_t 
                                                          const double *wt, int32_t S, double *part, uint32_t *ticket,
                                                          double *out) {
     __shared__ double red[4];
-    __shared__ uint32_t last;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l = blockIdx.y;
     const int64_t *ptr = sp.ptr[l];
@@ -120,12 +117,7 @@ __global__ __launch_bounds__(256) void steps_frob_kernel(int64_t n_sel, int32_t 
     if (lane == 0) red[w] = acc;
     __syncthreads();
     if (threadIdx.x == 0) part[(int64_t)l * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x * gridDim.y - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!block_is_last(ticket, gridDim.x * gridDim.y)) return;
     // the last block: step ll's partials summed in block order
     const int nb = gridDim.x;
     for (int ll = threadIdx.x; ll < L; ll += 256) {

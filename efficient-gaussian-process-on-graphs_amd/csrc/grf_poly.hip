@@ -24,14 +24,13 @@
 
 #include <algorithm>
 
+#include "grf_block.h"
 #include "grf_poly.h"
 
 namespace grf {
 namespace {
 
 constexpr int kKrylovBlocks = 512;  // row blocks of poly_krylov_frob_kernel (one fp64 partial each)
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __device__ inline double readlane_f64(double v, int j) {
     const uint64_t u = __builtin_bit_cast(uint64_t, v);
@@ -172,7 +171,6 @@ template <int NC>
 __global__ __launch_bounds__(256) void poly_step_colsq_kernel(int64_t n, PolyStep p, int32_t S, double *part,
                                                               uint32_t *ticket, double *out) {
     __shared__ double red[4][64 * NC];
-    __shared__ uint32_t last;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const PolyCols<NC> c = poly_cols<NC, true>(lane, S, p.unit);
     const double xs = p.xs ? *p.xs : 1.0;
@@ -192,12 +190,7 @@ __global__ __launch_bounds__(256) void poly_step_colsq_kernel(int64_t n, PolySte
     __syncthreads();
     for (int q = threadIdx.x; q < S; q += 256)
         part[(int64_t)blockIdx.x * S + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!block_is_last(ticket, gridDim.x)) return;
     for (int q = threadIdx.x; q < S; q += 256) {
         double sum = 0.0;
         for (unsigned bq = 0; bq < gridDim.x; ++bq) sum += __builtin_nontemporal_load(&part[(int64_t)bq * S + q]);
@@ -268,7 +261,6 @@ template <int NC, bool TWO, bool UNIT>
 __global__ __launch_bounds__(256) void poly_krylov_frob_kernel(int64_t n, KrylovStep p, int32_t S) {
     static_assert(!(TWO && UNIT), "the unit columns are one-sided");
     __shared__ double red[4];
-    __shared__ uint32_t last;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const bool from_unit = UNIT && p.x_unit;
     bool ok[NC];
@@ -373,12 +365,7 @@ __global__ __launch_bounds__(256) void poly_krylov_frob_kernel(int64_t n, Krylov
     if (lane == 0) red[w] = acc;
     __syncthreads();
     if (threadIdx.x == 0) p.part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(p.ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!block_is_last(p.ticket, gridDim.x)) return;
     if (threadIdx.x == 0) {
         double sum = 0.0;
         for (unsigned bq = 0; bq < gridDim.x; ++bq) sum += __builtin_nontemporal_load(&p.part[bq]);

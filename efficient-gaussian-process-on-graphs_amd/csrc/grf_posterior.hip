@@ -20,7 +20,7 @@
 
 #include <algorithm>
 
-#include "grf_common.h"
+#include "grf_block.h"
 
 namespace grf {
 namespace {
@@ -31,8 +31,6 @@ constexpr int kPostThreads = 64 * kPostWaves;
 constexpr int kPostBlocks = 256;    // row blocks at the most
 constexpr int kPostBlockIters = 4;  // a block has at least this many rows per lane before there is a second one
 constexpr int kPostBatch = 8;       // partials in flight per thread of the last block
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // log2 of the columns a wave's row group spans: the power of two >= min(S, 64)
 int post_lg_cols(int32_t S) { return ceil_log2((uint64_t)std::max(1, std::min(S, 64))); }
@@ -111,7 +109,6 @@ __global__ __launch_bounds__(kPostThreads) void posterior_reduce_kernel(int64_t 
                                                                double *mean) {
     constexpr int CP = 64 * NC;  // column slots
     __shared__ double red[2][kPostWaves][CP];
-    __shared__ uint32_t last;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int wave_rows = 64 >> lg_cols;
     const int rsub = lane >> lg_cols, cl = lane & ((1 << lg_cols) - 1);
@@ -169,12 +166,7 @@ __global__ __launch_bounds__(kPostThreads) void posterior_reduce_kernel(int64_t 
         pb[t] = qs;
         pb[S + t] = ms;
     }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!block_is_last(ticket, gridDim.x)) return;
     // the last block: G = threads / CP groups of consecutive blocks; a thread adds its column's partials of its
     // group in block order (kPostBatch loads in flight), then the groups are added in order
     constexpr int G = kPostThreads / CP;

@@ -44,8 +44,6 @@ constexpr int64_t kRowsMaxBlocks = 1 << 16;
 constexpr size_t kBigBudget = (size_t)256 << 20;    // bytes of bitmaps + ranks the big path aims to stay within
 constexpr int kBigMinWaves = GRF_SPGEMM_BIG_MIN_WAVES, kBigMaxWaves = GRF_SPGEMM_BIG_MAX_WAVES;
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct BigPlan {  // the workspace: [counters 256 B][row queue int32 n_rows][waves x (bitmap, ranks)]
     size_t queue_off, wave_off, bitmap_bytes, wave_bytes, total;
     int64_t words;

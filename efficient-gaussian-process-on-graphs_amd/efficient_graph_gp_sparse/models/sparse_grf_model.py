@@ -17,7 +17,7 @@ Subclasses ``gpytorch.models.ExactGP`` when gpytorch is installed; otherwise a
 """
 import torch
 
-from grf_amd.engine import DeviceCSR, WalkPolynomial, get_engine  # noqa: F401
+from grf_amd.engine import DeviceCSR, WalkPolynomial, get_engine, preconditioner_name  # noqa: F401
 from grf_amd.features import grf_marginal_log_likelihood, resolve_cg_tolerance
 
 from ..gptorch_kernels_sparse.sparse_grf_kernel import SparseGRFKernel
@@ -31,11 +31,6 @@ except ImportError:  # pragma: no cover - depends on the environment
 
 
 EVAL_CG_TOLERANCE = 1e-2  # gpytorch.settings.eval_cg_tolerance: the solves of a prediction
-
-
-def _check_preconditioner(preconditioner, what: str) -> None:
-    if preconditioner is not None and preconditioner != "jacobi":
-        raise ValueError(f"{what}: preconditioner must be None or \"jacobi\", not {preconditioner!r}")
 
 
 def _noise_value(likelihood) -> float:
@@ -94,7 +89,7 @@ class SparseGraphGP(_Base):
                 preconditioner=None):
         """(n_samples x n_test) posterior samples (float32, like the reference).  ``preconditioner="jacobi"``
         preconditions the solve by diag(K^) (fp64 only: with ``cg_dtype=torch.float32`` a ValueError)."""
-        _check_preconditioner(preconditioner, "predict")
+        preconditioner_name(preconditioner, "predict")
         if preconditioner is not None and cg_dtype != torch.float64:
             raise ValueError("predict: preconditioner=\"jacobi\" needs cg_dtype=torch.float64")
         dev = x_test.device
@@ -119,7 +114,7 @@ class SparseGraphGP(_Base):
         return out.to(torch.float32)
 
     def _moments(self, x_test, full_cov, tolerance, max_iter, add_noise, preconditioner=None):
-        _check_preconditioner(preconditioner, "predict_f")
+        preconditioner_name(preconditioner, "predict_f")
         dev = x_test.device
         eng = get_engine(dev if dev.type == "cuda" else None)
         op = self.covar_module._operator()

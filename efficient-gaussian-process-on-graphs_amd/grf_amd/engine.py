@@ -48,10 +48,32 @@ ROW_CUTS = os.environ.get("GRF_GRAM_CUTS", "auto")
 # skewed: the densest column of Phi holds at least this many times the mean column's entries (C4's
 # Erdos-Renyi Phi: ~1.2; Facebook / Enron: > 20)
 SKEW_RATIO = 4.0
+# the C solves by (family, float64, Lanczos coefficients, preconditioned) and their workspace sizes by
+# (family, preconditioned); "gram": Phi as a CSR, "poly": the walk operator
+CG_ENTRIES = {
+    ("gram", False, False, False): "grf_cg_gram_solve",
+    ("gram", True, False, False): "grf_cg_gram_solve_f64", ("gram", True, False, True): "grf_pcg_gram_solve_f64",
+    ("gram", True, True, False): "grf_cg_gram_solve_lanczos_f64",
+    ("gram", True, True, True): "grf_pcg_gram_solve_lanczos_f64",
+    ("poly", True, False, False): "grf_cg_poly_solve_f64", ("poly", True, False, True): "grf_pcg_poly_solve_f64",
+    ("poly", True, True, False): "grf_cg_poly_solve_lanczos_f64",
+    ("poly", True, True, True): "grf_pcg_poly_solve_lanczos_f64",
+}
+CG_WORKSPACES = {("gram", False): "grf_cg_workspace_bytes", ("gram", True): "grf_pcg_workspace_bytes",
+                 ("poly", False): "grf_cg_poly_workspace_bytes", ("poly", True): "grf_pcg_poly_workspace_bytes"}
 
 
 def _p(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def preconditioner_name(preconditioner, what: str) -> bool:
+    """True for "jacobi", False for None; anything else is refused (``what``: the caller, for the message)."""
+    if preconditioner is None:
+        return False
+    if isinstance(preconditioner, str) and preconditioner == "jacobi":
+        return True
+    raise ValueError(f"{what}: preconditioner must be None or \"jacobi\", not {preconditioner!r}")
 
 
 @dataclass
@@ -1177,15 +1199,6 @@ class GRFEngine:
             raise ValueError(f"{what}: precond must be a float64 tensor of {n_sys} inverse diagonal entries")
         return precond.to(self.device).flatten().contiguous()
 
-    @staticmethod
-    def _preconditioner_name(preconditioner, what: str) -> bool:
-        """True for "jacobi", False for None; anything else is refused."""
-        if preconditioner is None:
-            return False
-        if isinstance(preconditioner, str) and preconditioner == "jacobi":
-            return True
-        raise ValueError(f"{what}: preconditioner must be None or \"jacobi\", not {preconditioner!r}")
-
     def gram_jacobi(self, phi: DeviceCSR, rows=None, noise: float = 0.0) -> torch.Tensor:
         """dinv[r] = 1 / (sum_e Phi[rows[r], e]^2 + noise) = 1 / diag(Phi_T Phi_T^T + noise I)[r], fp64 on the
         device (grf_gram_jacobi_f64): the Jacobi preconditioner of ``cg_solve(precond=...)``.  The squares are
@@ -1230,32 +1243,31 @@ class GRFEngine:
             raise ValueError("cg_solve: return_lanczos needs a float64 B")
         dinv = self._precond(precond, n_sys, B, "cg_solve")
         phi_t = self.csr_transpose(phi, rmap) if phi_t is None else phi_t
-        S = B.shape[1]
+        operator = (n_sys, _p(phi.ptr), _p(phi.idx), _p(phi.val32), _p(rmap), phi.n_cols, _p(phi_t.ptr),
+                    _p(phi_t.idx), _p(phi_t.val32))
+        return self._cg_call("gram", operator, phi.n_cols, B, noise, tolerance, max_iter, dinv, return_residuals,
+                             return_lanczos)
+
+    def _cg_call(self, family: str, operator: tuple, n_inner: int, B: torch.Tensor, noise: float, tolerance: float,
+                 max_iter: int, dinv: Optional[torch.Tensor], return_residuals: bool, return_lanczos: bool):
+        """What cg_solve and cg_solve_poly share: one solve's buffers, its C entry from CG_ENTRIES called with the
+        operator's own arguments (n_sys first), the recurrence's and the entry's trailing ones, the return tuple."""
+        n_sys, S = operator[0], B.shape[1]
         X = torch.empty((n_sys, S), dtype=B.dtype, device=self.device)
-        wsb = self.lib.grf_cg_workspace_bytes if dinv is None else self.lib.grf_pcg_workspace_bytes
-        ws = self._ws(wsb(n_sys, phi.n_cols, S))
+        ws = self._ws(getattr(self.lib, CG_WORKSPACES[family, dinv is not None])(n_sys, n_inner, S))
         iters = ctypes.c_int32(0)
         resid = np.zeros(S, np.float64)
-        head = (n_sys, _p(phi.ptr), _p(phi.idx), _p(phi.val32), _p(rmap), phi.n_cols, _p(phi_t.ptr),
-                _p(phi_t.idx), _p(phi_t.val32), float(noise), _p(B), B.stride(0), S, float(tolerance),
-                int(max_iter), _p(X), X.stride(0), _p(ws), ws.numel(), ctypes.byref(iters),
-                resid.ctypes.data_as(ctypes.c_void_p))
+        args = operator + (float(noise), _p(B), B.stride(0), S, float(tolerance), int(max_iter), _p(X), X.stride(0),
+                           _p(ws), ws.numel(), ctypes.byref(iters), resid.ctypes.data_as(ctypes.c_void_p))
         coef = None
         if return_lanczos:
             coef = torch.empty((2 * max(int(max_iter), 0), S), dtype=torch.float64, device=self.device)
-            if dinv is not None:
-                C.check(self.lib.grf_pcg_gram_solve_lanczos_f64(*head, _p(coef), S, _p(dinv), self.stream),
-                        "grf_pcg_gram_solve_lanczos_f64")
-            else:
-                C.check(self.lib.grf_cg_gram_solve_lanczos_f64(*head, _p(coef), S, self.stream),
-                        "grf_cg_gram_solve_lanczos_f64")
-        elif dinv is not None:
-            C.check(self.lib.grf_pcg_gram_solve_f64(*head, _p(dinv), self.stream), "grf_pcg_gram_solve_f64")
-        else:
-            fn = self.lib.grf_cg_gram_solve if B.dtype == torch.float32 else self.lib.grf_cg_gram_solve_f64
-            C.check(fn(*head, self.stream), "grf_cg_gram_solve")
-        out = (X, int(iters.value)) + ((resid,) if return_residuals else ()) + ((coef,) if return_lanczos else ())
-        return out
+            args += (_p(coef), S)
+        if dinv is not None:
+            args += (_p(dinv),)
+        name = CG_ENTRIES[family, B.dtype == torch.float64, bool(return_lanczos), dinv is not None]
+        C.check(getattr(self.lib, name)(*args, self.stream), name)
+        return (X, int(iters.value)) + ((resid,) if return_residuals else ()) + ((coef,) if return_lanczos else ())
 
     # ------------------------------------- matrix-free marginal likelihood (CG + stochastic Lanczos quadrature)
     def steps_frob(self, steps, rows, A: torch.Tensor, WA: torch.Tensor, B: torch.Tensor, WB: torch.Tensor,
@@ -1348,30 +1360,11 @@ class GRFEngine:
         self._check_block(B, n_sys, "cg_solve_poly: B")
         dinv = self._precond(precond, n_sys, B, "cg_solve_poly")
         inv = self._inv_map(rmap, n)
-        S = B.shape[1]
-        X = torch.empty((n_sys, S), dtype=torch.float64, device=self.device)
-        wsb = self.lib.grf_cg_poly_workspace_bytes if dinv is None else self.lib.grf_pcg_poly_workspace_bytes
-        ws = self._ws(wsb(n_sys, n, S))
-        iters = ctypes.c_int32(0)
-        resid = np.zeros(S, np.float64)
         G, Gt = op.G, op.Gt
-        head = (n_sys, n, _p(G.ptr), _p(G.idx), _p(G.val), _p(Gt.ptr), _p(Gt.idx), _p(Gt.val), _p(ft), n_f, _p(rmap),
-                _p(inv), float(noise), _p(B), B.stride(0), S, float(tolerance), int(max_iter), _p(X), X.stride(0),
-                _p(ws), ws.numel(), ctypes.byref(iters), resid.ctypes.data_as(ctypes.c_void_p))
-        coef = None
-        if return_lanczos:
-            coef = torch.empty((2 * max(int(max_iter), 0), S), dtype=torch.float64, device=self.device)
-            if dinv is not None:
-                C.check(self.lib.grf_pcg_poly_solve_lanczos_f64(*head, _p(coef), S, _p(dinv), self.stream),
-                        "grf_pcg_poly_solve_lanczos_f64")
-            else:
-                C.check(self.lib.grf_cg_poly_solve_lanczos_f64(*head, _p(coef), S, self.stream),
-                        "grf_cg_poly_solve_lanczos_f64")
-        elif dinv is not None:
-            C.check(self.lib.grf_pcg_poly_solve_f64(*head, _p(dinv), self.stream), "grf_pcg_poly_solve_f64")
-        else:
-            C.check(self.lib.grf_cg_poly_solve_f64(*head, self.stream), "grf_cg_poly_solve_f64")
-        return (X, int(iters.value)) + ((resid,) if return_residuals else ()) + ((coef,) if return_lanczos else ())
+        operator = (n_sys, n, _p(G.ptr), _p(G.idx), _p(G.val), _p(Gt.ptr), _p(Gt.idx), _p(Gt.val), _p(ft), n_f,
+                    _p(rmap), _p(inv))
+        return self._cg_call("poly", operator, n, B, noise, tolerance, max_iter, dinv, return_residuals,
+                             return_lanczos)
 
     def poly_grad(self, op: WalkPolynomial, f, rows, A: torch.Tensor, B: torch.Tensor,
                   wt: torch.Tensor) -> torch.Tensor:
@@ -1655,55 +1648,40 @@ class GRFEngine:
         t = probes.shape[1]
         if not 1 <= t <= 255:
             raise ValueError("marginal_log_likelihood: between 1 and 255 probes per call")
-        jacobi = self._preconditioner_name(preconditioner, "marginal_log_likelihood")
+        jacobi = preconditioner_name(preconditioner, "marginal_log_likelihood")
         G = probes.detach().to(self.device, torch.float64)
-        poly = isinstance(steps, WalkPolynomial)
-        if not poly:
-            phi = steps.phi(f)
-            phi_t = self.csr_transpose(phi, tr)
+        op = kernel_operator(self, steps, f, tr, noise, "marginal_log_likelihood")
         if jacobi:
-            return self._mll_jacobi(steps, f, tr, yv, noise, G, tolerance, max_iter,
-                                    None if poly else (phi, phi_t))
+            return self._mll_jacobi(op, yv, G, tolerance, max_iter)
         rhs = torch.cat([yv[:, None], G], dim=1).contiguous()
-        if poly:
-            X, iters, coef = self.cg_solve_poly(steps, f, rhs, noise, tr, tolerance, max_iter, return_lanczos=True)
-        else:
-            X, iters, coef = self.cg_solve(phi, rhs, noise, tr, phi_t, tolerance, max_iter, return_lanczos=True)
+        X, iters, coef = op.solve(rhs, tolerance, max_iter, return_lanczos=True)
         # the weighted column sums both scalars need, one host read with the coefficients' probe columns
         wt = torch.full((1 + t,), -0.5 / t, dtype=torch.float64, device=self.device)
         wt[0] = 0.5
         cols = torch.stack([(rhs * X).sum(0), (X * X).sum(0), (rhs * rhs).sum(0)]).cpu().numpy()
-        logdet = self.slq_logdet(coef[:, 1:].cpu().numpy(), iters, cols[2, 1:])
-        value = -0.5 * cols[0, 0] - 0.5 * logdet - 0.5 * n * float(np.log(2.0 * np.pi))
-        # d/ds2: dK = I -> 1/2 a.a - 1/(2t) sum_i u_i.z_i
-        g_noise = 0.5 * cols[1, 0] - 0.5 / t * float(cols[0, 1:].sum())
+        lanczos = coef[:, 1:].cpu().numpy()
         # d/df_l: dK = M_l[T] Phi_T^T + Phi_T M_l[T]^T; the y column pairs a with itself
         Bm = rhs
         Bm[:, 0] = X[:, 0]
-        if poly:
-            return float(value), self.poly_grad(steps, f, tr, X, Bm, wt), float(g_noise), iters
-        WX = self.spmm(phi_t, X)
-        WB = self.spmm(phi_t, Bm)
-        n_f = min(int(f.numel()), steps.L)
-        g_f = self.steps_frob(steps, tr, X, WX, Bm, WB, wt, n_steps=n_f)
-        return float(value), g_f, float(g_noise), iters
+        # d/ds2: dK = I -> 1/2 a.a - 1/(2t) sum_i u_i.z_i (row 0 of cols)
+        return self._mll_tail(op, X, Bm, wt, cols, lanczos, iters, 0.0, 0)
 
-    def _mll_jacobi(self, steps, f, tr, yv, noise, G, tolerance, max_iter, phis):
-        """marginal_log_likelihood's Jacobi route (see there); phis = (Phi, Phi_T^T), or None for the operator."""
-        n, t = G.shape
-        if phis is None:
-            dinv = self.poly_jacobi(steps, f, tr, noise)
-        else:
-            phi, phi_t = phis
-            dinv = self.gram_jacobi(phi, tr, noise)
+    def _mll_tail(self, op, X, Bm, wt, cols, lanczos, iters, logdet_d, trace_row):
+        """The end of both routes of marginal_log_likelihood.  cols (3 x (1 + t), host): [0, 0] y.a, [1, 0] a.a,
+        [trace_row, 1:] the probes' terms of tr(K^-1), [2, 1:] their squared norms; logdet_d: the route's log det D."""
+        n, t = X.shape[0], X.shape[1] - 1
+        logdet = logdet_d + self.slq_logdet(lanczos, iters, cols[2, 1:])
+        value = -0.5 * cols[0, 0] - 0.5 * logdet - 0.5 * n * float(np.log(2.0 * np.pi))
+        g_noise = 0.5 * cols[1, 0] - 0.5 / t * float(cols[trace_row, 1:].sum())
+        return float(value), op.modulator_grad(X, Bm, wt), float(g_noise), iters
+
+    def _mll_jacobi(self, op, yv, G, tolerance, max_iter):
+        """marginal_log_likelihood's Jacobi route (see there) on the kernel operator ``op``."""
+        t = G.shape[1]
+        dinv = op.jacobi()
         sq = torch.sqrt(dinv)[:, None]                                         # D^-1/2
         rhs = torch.cat([yv[:, None], G / sq], dim=1).contiguous()             # [y | D^1/2 g_i]
-        if phis is None:
-            X, iters, coef = self.cg_solve_poly(steps, f, rhs, noise, tr, tolerance, max_iter, return_lanczos=True,
-                                                precond=dinv)
-        else:
-            X, iters, coef = self.cg_solve(phi, rhs, noise, tr, phi_t, tolerance, max_iter, return_lanczos=True,
-                                           precond=dinv)
+        X, iters, coef = op.solve(rhs, tolerance, max_iter, precond=dinv, return_lanczos=True)
         Bm = torch.cat([X[:, :1], G * sq], dim=1).contiguous()                 # [a | D^-1 z_i = D^-1/2 g_i]
         wt = torch.full((1 + t,), -0.5 / t, dtype=torch.float64, device=self.device)
         wt[0] = 0.5
@@ -1712,26 +1690,14 @@ class GRFEngine:
         # as a_k.a_k + 2 w.r_k with r_k = y - K^ a_k and w ~ K^-1 a_k from one more one-column solve:
         # y^T K^-1 a_k = a_k.a_k + w.r_k and a_k.(a - a_k) = w.r_k, each up to a product of two solve errors
         a = X[:, :1].contiguous()
-        if phis is None:
-            r = yv[:, None] - self.poly_gram_matvec(steps, f, a, rows=tr, cols=tr, noise=noise)
-            w, _ = self.cg_solve_poly(steps, f, a, noise, tr, tolerance, max_iter, precond=dinv)
-        else:
-            r = yv[:, None] - self.gram_matvec(phi, a, rows=tr, cols=tr, phi_t=phi_t, noise=noise)
-            w, _ = self.cg_solve(phi, a, noise, tr, phi_t, tolerance, max_iter, precond=dinv)
+        r = yv[:, None] - op.matvec(a)
+        w, _ = op.solve(a, tolerance, max_iter, precond=dinv)
         quad = (Bm * X).sum(0)
         quad[0] = quad[0] + 2.0 * (w * r).sum()
         cols = torch.stack([(rhs * X).sum(0), quad, torch.cat([dinv.log().sum()[None], (G * G).sum(0)])])
         cols = cols.cpu().numpy()
-        logdet = -cols[2, 0] + self.slq_logdet(coef[:, 1:].cpu().numpy(), iters, cols[2, 1:])
-        value = -0.5 * cols[0, 0] - 0.5 * logdet - 0.5 * n * float(np.log(2.0 * np.pi))
-        g_noise = 0.5 * cols[1, 0] - 0.5 / t * float(cols[1, 1:].sum())
-        if phis is None:
-            return float(value), self.poly_grad(steps, f, tr, X, Bm, wt), float(g_noise), iters
-        WX = self.spmm(phi_t, X)
-        WB = self.spmm(phi_t, Bm)
-        n_f = min(int(f.numel()), steps.L)
-        g_f = self.steps_frob(steps, tr, X, WX, Bm, WB, wt, n_steps=n_f)
-        return float(value), g_f, float(g_noise), iters
+        # log det K^ = -sum log dinv + the quadrature of D^-1/2 K^ D^-1/2; the trace terms are quad's (row 1)
+        return self._mll_tail(op, X, Bm, wt, cols, coef[:, 1:].cpu().numpy(), iters, -cols[2, 0], 1)
 
     def pathwise_predict(self, phi: DeviceCSR, train_idx, test_idx, y_train: torch.Tensor, noise: float,
                          eps1: torch.Tensor, eps2: torch.Tensor, tolerance: float = 1.0, max_iter: int = 1000,
@@ -1748,29 +1714,17 @@ class GRFEngine:
         by diag(K^).  Returns (S x n_test) posterior samples (dtype) and the CG iteration count."""
         tr = self._row_map(train_idx)
         te = self._row_map(test_idx)
-        jacobi = self._preconditioner_name(preconditioner, "pathwise_predict")
+        jacobi = preconditioner_name(preconditioner, "pathwise_predict")
         if jacobi and dtype != torch.float64:
             raise ValueError("pathwise_predict: a preconditioned solve runs in float64 only")
-        if isinstance(phi, WalkPolynomial):
-            if f is None or dtype != torch.float64:
-                raise ValueError("pathwise_predict: a WalkPolynomial needs its modulator f and dtype float64")
-            E = eps1.to(self.device, dtype).t().contiguous()
-            FE = self.poly_apply(phi, f, E)                                    # p(G) E: every node's prior draw
-            y = y_train.to(self.device, dtype).flatten()
-            B = y[:, None] - (FE[tr.long()] + eps2.to(self.device, dtype).t())
-            V, iters = self.cg_solve_poly(phi, f, B.contiguous(), noise, tr, tolerance, max_iter,
-                                          precond=self.poly_jacobi(phi, f, tr, noise) if jacobi else None)
-            out = FE[te.long()] + self.poly_gram_matvec(phi, f, V, rows=te, cols=tr)
-            return out.t(), iters
+        op = kernel_operator(self, phi, f, tr, noise, "pathwise_predict", dtype)
         E = eps1.to(self.device, dtype).t().contiguous()                      # n_nodes x S
-        f_train = self.spmm(phi, E, tr)                                        # (eps1 @ phi_train.T)^T
-        f_test = self.spmm(phi, E, te)
+        f_train = op.prior_draw(E, tr)                                         # (eps1 @ phi_train.T)^T
+        f_test = op.prior_draw(E, te)
         y = y_train.to(self.device, dtype).flatten()
         B = y[:, None] - (f_train + eps2.to(self.device, dtype).t())          # b_batch^T
-        phi_t = self.csr_transpose(phi, tr)
-        V, iters = self.cg_solve(phi, B.contiguous(), noise, tr, phi_t, tolerance, max_iter,
-                                 precond=self.gram_jacobi(phi, tr, noise) if jacobi else None)
-        out = f_test + self.spmm(phi, self.spmm(phi_t, V), te)                # + K_test_train v
+        V, iters = op.solve(B.contiguous(), tolerance, max_iter, precond=op.jacobi() if jacobi else None)
+        out = f_test + op.cross(te, V)                                         # + K_test_train v
         return out.t(), iters
 
     # ------------------------------------- the exact posterior mean and variance (predict_f)
@@ -1847,20 +1801,17 @@ class GRFEngine:
         ``preconditioner="jacobi"``: 1 / diag(K^) is built once and preconditions every solve (alpha and each
         chunk); the energy form bounds b^T K^-1 b from below for any x, so the statement on the variances holds
         for the preconditioned iterates unchanged."""
-        jacobi = self._preconditioner_name(preconditioner, "posterior_moments")
-        poly = isinstance(phi, WalkPolynomial)
-        if poly and f is None:
-            raise ValueError("posterior_moments: a WalkPolynomial needs its modulator f")
+        jacobi = preconditioner_name(preconditioner, "posterior_moments")
         tr, te = self._row_map(train_idx), self._row_map(test_idx)
+        op = kernel_operator(self, phi, f, tr, noise, "posterior_moments")
         n, ns = tr.numel(), te.numel()
         y = y_train.detach().to(self.device, torch.float64).flatten()
         if y.numel() != n:
             raise ValueError("posterior_moments: y_train must hold one value per training node")
-        n_nodes = phi.shape[0] if poly else phi.n_cols
         chunk = self.POSTERIOR_CHUNK
         if full_cov:  # B for every test node, its transpose for the product, the result and its symmetrisation
             self._dense_memory_guard("posterior_moments (full_cov)", max(n, ns),
-                                     2 * n * ns * 8 + 2 * ns * ns * 8 + (0 if poly else n_nodes * min(chunk, ns) * 8))
+                                     2 * n * ns * 8 + 2 * ns * ns * 8 + op.scratch_rows * min(chunk, ns) * 8)
         mean = torch.zeros(ns, dtype=torch.float64, device=self.device)
         var = torch.empty(ns, dtype=torch.float64, device=self.device)
         iters, alpha_iters = [], 0
@@ -1868,23 +1819,16 @@ class GRFEngine:
             info["cg_iterations"], info["alpha_iterations"] = iters, 0
         if ns == 0:
             return mean, (torch.empty((0, 0), dtype=torch.float64, device=self.device) if full_cov else var)
-        phi_t, alpha, dinv = None, None, None
+        alpha, dinv = None, None
         if n:
-            if poly:
-                dinv = self.poly_jacobi(phi, f, tr, noise) if jacobi else None
-                alpha, alpha_iters = self.cg_solve_poly(phi, f, y[:, None].contiguous(), noise, tr, tolerance, max_iter,
-                                                        precond=dinv)
-            else:
-                phi_t = self.csr_transpose(phi, tr)
-                dinv = self.gram_jacobi(phi, tr, noise) if jacobi else None
-                alpha, alpha_iters = self.cg_solve(phi, y[:, None].contiguous(), noise, tr, phi_t, tolerance, max_iter,
-                                                   precond=dinv)
+            dinv = op.jacobi() if jacobi else None
+            alpha, alpha_iters = op.solve(y[:, None].contiguous(), tolerance, max_iter, precond=dinv)
             alpha = alpha.flatten()
         if info is not None:
             info["alpha_iterations"] = alpha_iters
         width = min(chunk, ns)
         prior = torch.empty(ns, dtype=torch.float64, device=self.device)
-        E_buf = None if poly else torch.empty((n_nodes, width), dtype=torch.float64, device=self.device)
+        E_buf = torch.empty((op.scratch_rows, width), dtype=torch.float64, device=self.device)
         B_all = torch.empty((n, ns if full_cov else width), dtype=torch.float64, device=self.device)
         cov = torch.empty((ns, ns), dtype=torch.float64, device=self.device) if full_cov else None
         extra = float(noise) if add_noise else 0.0
@@ -1892,42 +1836,20 @@ class GRFEngine:
 
         def rhs(c0, c1):
             """B[:, c0:c1] = K[T, chunk] (a window of B_all), prior[c0:c1], and cov[:, c0:c1] = K[x, chunk]."""
-            S = c1 - c0
-            nodes = te[c0:c1]
-            Bv = B_all[:, c0:c1] if full_cov else B_all[:, :S]
-            if poly:
-                if n:
-                    Bv.copy_(self.poly_kernel_block(phi, f, x1=tr, x2=nodes))
-                prior[c0:c1] = self.poly_kernel_diag(phi, f, x=nodes)
-                if full_cov:
-                    cov[:, c0:c1] = self.poly_kernel_block(phi, f, x1=te, x2=nodes)
-                return Bv
-            E = E_buf[:, :S]
-            self.posterior_rhs(phi, nodes, E, prior[c0:c1])
-            if n:
-                self.spmm(phi, E, tr, out=Bv)
-            if full_cov:
-                self.spmm(phi, E, te, out=cov[:, c0:c1])
+            Bv = B_all[:, c0:c1] if full_cov else B_all[:, :c1 - c0]
+            op.columns(te[c0:c1], Bv, prior[c0:c1], E_buf, te, cov[:, c0:c1] if full_cov else None)
             return Bv
 
         def solve(Bv, c0, c1):
-            if n:
-                if poly:
-                    X, it = self.cg_solve_poly(phi, f, Bv, noise, tr, tolerance, max_iter, precond=dinv)
-                else:
-                    X, it = self.cg_solve(phi, Bv, noise, tr, phi_t, tolerance, max_iter, precond=dinv)
-            else:
-                X, it = Bv, 0
-            iters.append(it)
             if not n:
-                self.posterior_reduce(Bv, X, prior[c0:c1], None, extra, var[c0:c1])
-                return X
+                iters.append(0)
+                self.posterior_reduce(Bv, Bv, prior[c0:c1], None, extra, var[c0:c1])
+                return Bv
+            X, it = op.solve(Bv, tolerance, max_iter, precond=dinv)
+            iters.append(it)
             # b^T x alone is below b^T K^-1 b only while CG keeps r_k orthogonal to its Krylov space; the
             # energy form 2 b^T x - x^T K^ x = x^T (2 b - K^ x) is below it for any x, so the variance uses that
-            if poly:
-                KX = self.poly_gram_matvec(phi, f, X, rows=tr, cols=tr, noise=noise)
-            else:
-                KX = self.gram_matvec(phi, X, rows=tr, cols=tr, phi_t=phi_t, noise=noise)
+            KX = op.matvec(X)
             KX.mul_(-1.0).add_(Bv, alpha=2.0)
             self.posterior_reduce(KX, X, prior[c0:c1], None, extra, var[c0:c1])
             self.posterior_reduce(Bv, X, prior[c0:c1], alpha, 0.0, scratch[:c1 - c0], mean[c0:c1])
@@ -1962,6 +1884,111 @@ class GRFEngine:
         slots = self.walk(G, walks_per_node, p_halt, max_walk_length, rng=rng, seed=seed, n_chunks=n_chunks)
         phi = self.compact(self.features(slots, modulator_vector, norm))
         return self.gram(phi, method)
+
+
+class PhiOperator:
+    """K^ = Phi_T Phi_T^T + noise I, T = ``tr``, for Phi as a DeviceCSR (or the step matrices it is made of, with
+    ``f``), as marginal_log_likelihood, pathwise_predict and posterior_moments use it; made once per call.  Phi_T^T
+    is transposed once: with the step matrices at once, otherwise before the first Jacobi diagonal or solve."""
+
+    def __init__(self, eng: "GRFEngine", phi, f, tr: torch.Tensor, noise: float):
+        self.eng, self.f, self.tr, self.noise, self.steps, self._phi_t = eng, f, tr, noise, None, None
+        if isinstance(phi, DeviceCSR):
+            self.phi = phi
+        else:
+            self.steps, self.phi = phi, phi.phi(f)
+            self.phi_t()
+        self.scratch_rows = self.phi.n_cols   # rows of columns()' scratch block, Phi[nodes]^T
+
+    def phi_t(self) -> DeviceCSR:
+        if self._phi_t is None:
+            self._phi_t = self.eng.csr_transpose(self.phi, self.tr)
+        return self._phi_t
+
+    def jacobi(self) -> torch.Tensor:
+        self.phi_t()
+        return self.eng.gram_jacobi(self.phi, self.tr, self.noise)
+
+    def solve(self, B, tolerance, max_iter, precond=None, return_lanczos=False):
+        return self.eng.cg_solve(self.phi, B, self.noise, self.tr, self.phi_t(), tolerance, max_iter,
+                                 return_lanczos=return_lanczos, precond=precond)
+
+    def cross(self, rows, V, noise=0.0):
+        """K[rows, T] V (+ noise V)."""
+        return self.eng.gram_matvec(self.phi, V, rows=rows, cols=self.tr, phi_t=self.phi_t(), noise=noise)
+
+    def matvec(self, V):
+        return self.cross(self.tr, V, self.noise)   # K^ V, the noise term included
+
+    def prior_draw(self, E, rows):
+        """(Phi E)[rows]: the rows of the prior sample with the weights E (n_nodes x S)."""
+        return self.eng.spmm(self.phi, E, rows)
+
+    def columns(self, nodes, Bv, prior, scratch, test_rows, cov=None):
+        """Bv = K[T, nodes], prior = diag K[nodes] and, when given, cov = K[test_rows, nodes], into the caller's
+        windows; scratch: its (scratch_rows x >= len(nodes)) block."""
+        E = scratch[:, :nodes.numel()]
+        self.eng.posterior_rhs(self.phi, nodes, E, prior)
+        if self.tr.numel():
+            self.eng.spmm(self.phi, E, self.tr, out=Bv)
+        if cov is not None:
+            self.eng.spmm(self.phi, E, test_rows, out=cov)
+
+    def modulator_grad(self, X, Bm, wt):
+        """out[l] = sum_c wt[c] x_c^T (dK/df_l) b_c, dK/df_l = M_l[T] Phi_T^T + Phi_T M_l[T]^T (needs the steps)."""
+        WX = self.eng.spmm(self.phi_t(), X)
+        WB = self.eng.spmm(self.phi_t(), Bm)
+        n_f = min(int(self.f.numel()), self.steps.L)
+        return self.eng.steps_frob(self.steps, self.tr, X, WX, Bm, WB, wt, n_steps=n_f)
+
+
+class WalkOperator:
+    """The same methods for the exact kernel K = S p(G) p(G)^T S^T of a WalkPolynomial with its modulator ``f``
+    (fp64 only): Horner chains with the walk matrix, neither Phi nor a power of G formed."""
+    scratch_rows = 0
+
+    def __init__(self, eng: "GRFEngine", op: WalkPolynomial, f, tr: torch.Tensor, noise: float):
+        self.eng, self.op, self.f, self.tr, self.noise, self._draw = eng, op, f, tr, noise, None
+
+    def jacobi(self) -> torch.Tensor:
+        return self.eng.poly_jacobi(self.op, self.f, self.tr, self.noise)
+
+    def solve(self, B, tolerance, max_iter, precond=None, return_lanczos=False):
+        return self.eng.cg_solve_poly(self.op, self.f, B, self.noise, self.tr, tolerance, max_iter,
+                                      return_lanczos=return_lanczos, precond=precond)
+
+    def cross(self, rows, V, noise=0.0):
+        return self.eng.poly_gram_matvec(self.op, self.f, V, rows=rows, cols=self.tr, noise=noise)
+
+    def matvec(self, V):
+        return self.cross(self.tr, V, self.noise)
+
+    def prior_draw(self, E, rows):
+        """(p(G) E)[rows]; one chain per E gives every node's draw, kept for the next rows."""
+        if self._draw is None or self._draw[0] is not E:
+            self._draw = (E, self.eng.poly_apply(self.op, self.f, E))
+        return self._draw[1][rows.long()]
+
+    def columns(self, nodes, Bv, prior, scratch, test_rows, cov=None):
+        if self.tr.numel():
+            Bv.copy_(self.eng.poly_kernel_block(self.op, self.f, x1=self.tr, x2=nodes))
+        prior.copy_(self.eng.poly_kernel_diag(self.op, self.f, x=nodes))
+        if cov is not None:
+            cov.copy_(self.eng.poly_kernel_block(self.op, self.f, x1=test_rows, x2=nodes))
+
+    def modulator_grad(self, X, Bm, wt):
+        return self.eng.poly_grad(self.op, self.f, self.tr, X, Bm, wt)
+
+
+def kernel_operator(eng: GRFEngine, phi, f, tr: torch.Tensor, noise: float, what: str, dtype=None):
+    """The one place that asks "Phi as a CSR, or the walk operator?": a PhiOperator (a DeviceCSR or StepMatrices) or
+    a WalkOperator (a WalkPolynomial: needs ``f`` and, where the caller ``what`` has a ``dtype`` to choose, float64)."""
+    if not isinstance(phi, WalkPolynomial):
+        return PhiOperator(eng, phi, f, tr, noise)
+    if f is None or dtype not in (None, torch.float64):
+        raise ValueError(f"{what}: a WalkPolynomial needs its modulator f" +
+                         (" and dtype float64" if dtype is not None else ""))
+    return WalkOperator(eng, phi, f, tr, noise)
 
 
 _engines: dict = {}

@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib as C
-from .engine import DeviceCSR, GRFEngine, WalkPolynomial, _p, cols_band_width, get_engine  # noqa: F401
+from .engine import (DeviceCSR, GRFEngine, WalkPolynomial, _p, cols_band_width, get_engine,  # noqa: F401
+                     preconditioner_name)
 
 
 def _torch_csr(mat) -> torch.Tensor:
@@ -360,9 +361,7 @@ def grf_marginal_log_likelihood(f: torch.Tensor, noise, steps, train_idx, y, pro
     value and the gradients estimate the same quantities (``GRFEngine.marginal_log_likelihood``); typically
     several times fewer CG iterations on the walk estimator's Phi."""
     eng = steps.engine
-    if preconditioner is not None and preconditioner != "jacobi":
-        raise ValueError(f"grf_marginal_log_likelihood: preconditioner must be None or \"jacobi\", not "
-                         f"{preconditioner!r}")
+    preconditioner_name(preconditioner, "grf_marginal_log_likelihood")
     idx = torch.as_tensor(train_idx).flatten()
     n = idx.numel()
     yt = torch.as_tensor(y).flatten()

@@ -25,6 +25,44 @@ def test_workspaces_hold_the_second_partial_sums():
         assert lib.grf_pcg_poly_workspace_bytes(n_sys, n_cols, s) >= plain + 256 * s * 8 - 256
 
 
+# the four workspace sizes at (n_sys, n_cols | n, n_rhs), GRF_SPMM_TILE_BYTES unset: literals read from the build of the
+# commit before the layouts were folded into one base layout (the engine sizes its buffers by these functions, so
+# any moved or resized buffer shows here)
+PINNED_WORKSPACES = {
+    "grf_cg_workspace_bytes": (3840, 2749696, 1046936832),
+    "grf_pcg_workspace_bytes": (5888, 2880768, 1047461120),
+    "grf_cg_poly_workspace_bytes": (4352, 5522688, 1434136832),
+    "grf_pcg_poly_workspace_bytes": (6400, 5653760, 1434661120),
+}
+
+
+def test_workspace_sizes_are_pinned():
+    import os
+    from grf_amd import _lib
+    assert "GRF_SPMM_TILE_BYTES" not in os.environ, \
+        "GRF_SPMM_TILE_BYTES is set: the sizes are pinned for the default tile budget (8 MiB); unset it"
+    lib = _lib.load()
+    shapes = ((1, 1, 1), (600, 2708, 64), (100000, 100000, 256))
+    for name, sizes in PINNED_WORKSPACES.items():
+        assert tuple(getattr(lib, name)(*a) for a in shapes) == sizes, name
+
+
+def test_messages_name_the_entry_that_was_called():
+    from grf_amd import _lib
+    lib = _lib.load()
+    d = ctypes.c_void_p(8)  # (never dereferenced: a bad stride is refused before anything is read)
+    tail = (0.1, d, 3, 4, 1.0, 5, d, 4, d, 1 << 40, None, None)   # ld_rhs = 3 < n_rhs = 4
+    gram = (4, d, d, d, None, 8, d, d, d) + tail
+    poly = (4, 8, d, d, d, d, d, d, d, 2, d, d) + tail
+    for fn, args, family in ((lib.grf_cg_gram_solve_f64, gram + (None,), b"grf_cg_gram_solve"),
+                             (lib.grf_pcg_gram_solve_f64, gram + (d, None), b"grf_pcg_gram_solve"),
+                             (lib.grf_cg_poly_solve_f64, poly + (None,), b"grf_cg_poly_solve"),
+                             (lib.grf_pcg_poly_solve_f64, poly + (d, None), b"grf_pcg_poly_solve")):
+        assert fn(*args) == _lib.GRF_EINVAL
+        err = lib.grf_last_error()
+        assert b"strides" in err and err.startswith(family), err
+
+
 def test_argument_checks_need_no_device():
     from grf_amd import _lib
     lib = _lib.load()
