@@ -31,6 +31,7 @@ int32_t grf_device_count(void) {
 }
 
 int32_t grf_set_device(int32_t device) {
+    GRF_REQUIRE(device >= 0, GRF_EINVAL, "grf_set_device: device must be >= 0 (got %d)", device);
     GRF_CHECK_HIP(hipSetDevice(device));
     return GRF_OK;
 }

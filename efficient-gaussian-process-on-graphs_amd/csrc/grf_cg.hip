@@ -789,6 +789,7 @@ static int32_t cg_gram_solve(int64_t n_sys, const int64_t *ptr, const int32_t *i
                              const int32_t *row_map, int64_t n_cols, const int64_t *t_ptr, const int32_t *t_idx,
                              const float *t_val, double noise, const CgCall<T> &c) {
     GRF_REQUIRE(n_sys > 0 && n_cols > 0 && ptr && t_ptr, GRF_EINVAL, "%s: bad arguments", c.who);
+    GRF_REQUIRE(noise == noise, GRF_EINVAL, "%s: the noise is NaN", c.who);
     if (const int32_t rc = cg_check_call(c); rc != GRF_OK) return rc;
     const CgLayout l = cg_layout(n_sys, n_cols, c.n_rhs, sizeof(T), c.pre ? 2 : 1);
     GramMatVec<T> mv{n_sys, ptr, idx, val, row_map, n_cols, t_ptr, t_idx, t_val, noise, l};
@@ -843,6 +844,8 @@ extern "C" {
 #pragma GCC visibility push(default)
 
 size_t grf_csr_transpose_workspace_bytes(int64_t n_sel, int64_t n_cols, int64_t nnz) {
+    if (n_sel > kMaxIds || n_cols > kMaxIds || nnz > kMaxEntries) return kSizeSaturated;
+    if (n_sel < 0) n_sel = 0;
     const int64_t z = std::max<int64_t>(nnz, 1);
     return al256((size_t)(n_sel + 1) * 4) + al256((size_t)(n_sel + 1) * 8) + scan_ws_bytes(n_sel + 1) +
            2 * al256((size_t)z * 4) + 2 * al256((size_t)z * 8) + al256(csr_tr_sort_temp_bytes(nnz, n_cols));
@@ -853,10 +856,14 @@ int32_t grf_csr_transpose(int64_t n_sel, const int64_t *ptr, const int32_t *idx,
                           float *t_val, void *workspace, size_t workspace_bytes, grf_stream_t stream) {
     // (idx / val / t_idx / t_val may be NULL when there are no entries)
     GRF_REQUIRE(n_sel >= 0 && n_cols > 0 && nnz >= 0 && ptr && t_ptr, GRF_EINVAL, "grf_csr_transpose: bad arguments");
+    GRF_REQUIRE(n_sel < (1ll << 31) && n_cols < (1ll << 31), GRF_EUNSUPPORTED, "grf_csr_transpose: more than 2^31 rows");
     const size_t need = grf_csr_transpose_workspace_bytes(n_sel, n_cols, nnz);
     GRF_REQUIRE(workspace && workspace_bytes >= need, GRF_EINVAL, "grf_csr_transpose: workspace too small (%zu < %zu)",
                 workspace_bytes, need);
-    GRF_REQUIRE(n_sel < (1ll << 31) && n_cols < (1ll << 31), GRF_EUNSUPPORTED, "grf_csr_transpose: more than 2^31 rows");
+    // every launch below, checked before the first one (csr_tr_len_kernel's cdiv(n_sel, 256) x 256 fits for any
+    // n_sel < 2^31)
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n_sel, 4), 256, "csr_tr_gather_kernel");
+    GRF_REQUIRE_GRID(cdiv<int64_t>(nnz + 1, 256), 256, "csr_tr_unpack_kernel");
     hipStream_t st = S(stream);
     const int64_t z = std::max<int64_t>(nnz, 1);
     char *w = (char *)workspace;
@@ -876,7 +883,6 @@ int32_t grf_csr_transpose(int64_t n_sel, const int64_t *ptr, const int32_t *idx,
         GRF_CHECK_LAUNCH("csr_tr_len_kernel");
         int32_t rc = scan_counts_i32(n_sel, len, off, scan_ws, scan_ws_bytes(n_sel + 1), st);
         if (rc != GRF_OK) return rc;
-        GRF_REQUIRE_GRID(cdiv<int64_t>(n_sel, 4), 256, "csr_tr_gather_kernel");
         csr_tr_gather_kernel<<<(unsigned)cdiv<int64_t>(n_sel, 4), 256, 0, st>>>(n_sel, ptr, idx, val, row_map, off, k0,
                                                                                v0);
         GRF_CHECK_LAUNCH("csr_tr_gather_kernel");
@@ -891,7 +897,6 @@ int32_t grf_csr_transpose(int64_t n_sel, const int64_t *ptr, const int32_t *idx,
         GRF_CHECK_HIP(rocprim::radix_sort_pairs(w, temp_bytes, (const uint32_t *)k0, k1, (const uint64_t *)v0, v1,
                                                 (size_t)nnz, 0u, key_bits(n_cols), st));
     }
-    GRF_REQUIRE_GRID(cdiv<int64_t>(nnz + 1, 256), 256, "csr_tr_unpack_kernel");
     csr_tr_unpack_kernel<<<(unsigned)cdiv<int64_t>(nnz + 1, 256), 256, 0, st>>>(nnz, n_cols, k1, v1, t_ptr, t_idx,
                                                                                 t_val);
     GRF_CHECK_LAUNCH("csr_tr_unpack_kernel");

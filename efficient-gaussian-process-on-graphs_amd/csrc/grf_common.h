@@ -68,6 +68,17 @@ __device__ inline int32_t uniform32(int32_t v) { return __builtin_amdgcn_readfir
         }                                                                                \
     } while (0)
 
+// Sizes the entries accept: node, row and column counts fit the int32 ids the CSR arrays hold; entry counts
+// (nnz, buckets) stay below 2^40.  A size function given an argument beyond them saturates -- SIZE_MAX (INT64_MAX
+// for the int64 bounds), never a small wrapped value -- so no workspace_bytes satisfies it.
+constexpr int64_t kMaxIds = 0x7fffffffLL;
+constexpr int64_t kMaxEntries = 1ll << 40;
+constexpr size_t kSizeSaturated = ~(size_t)0;
+constexpr int64_t kBoundSaturated = INT64_MAX;
+
+#define GRF_REQUIRE_IDS(v, who, what)                                                     \
+    GRF_REQUIRE((int64_t)(v) <= kMaxIds, GRF_EUNSUPPORTED, "%s: %s must fit int32 ids", who, what)
+
 // The dispatcher takes at most 2^32 - 1 work-items per launch (gridDim.x * blockDim.x):
 // a larger grid is silently truncated on gfx950, so every variable-size launch checks it.
 #define GRF_REQUIRE_GRID(blocks, threads, name)                                          \

@@ -155,6 +155,7 @@ int32_t grf_dense_steps_phi(int64_t n, int32_t L, const double *F, const double 
                             int64_t lda32, grf_stream_t stream) {
     GRF_REQUIRE(n >= 0 && L >= 1 && lda32 >= n && (n == 0 || (F && f && phi32)), GRF_EINVAL,
                 "grf_dense_steps_phi: bad arguments");
+    GRF_REQUIRE_IDS(n, "grf_dense_steps_phi", "n");
     if (n == 0) return GRF_OK;
     const int64_t work = n * lda32;
     GRF_REQUIRE_GRID(cdiv<int64_t>(work, 256), 256, "dense_steps_phi_kernel");
@@ -165,14 +166,18 @@ int32_t grf_dense_steps_phi(int64_t n, int32_t L, const double *F, const double 
 }
 
 size_t grf_dense_steps_grad_workspace_bytes(int64_t n, int32_t L) {
+    if (n > kMaxIds) return kSizeSaturated;
     const int64_t nt = cdiv<int64_t>(n > 0 ? n : 1, (int64_t)kGT);
-    return (size_t)(nt * nt) * (size_t)(L > 0 ? L : 1) * sizeof(double);
+    const size_t blocks = (size_t)(nt * nt), steps = (size_t)(L > 0 ? L : 1);  // (nt <= 2^25: nt * nt fits)
+    if (blocks > kSizeSaturated / sizeof(double) / steps) return kSizeSaturated;  // (the product would wrap)
+    return blocks * steps * sizeof(double);
 }
 
 int32_t grf_dense_steps_grad(int64_t n, int32_t L, const double *F, const double *phi64, const double *G, int64_t ldg,
                              double *grad, void *workspace, size_t workspace_bytes, grf_stream_t stream) {
     GRF_REQUIRE(n >= 0 && L >= 1 && ldg >= n && grad && (n == 0 || (F && phi64 && G && workspace)), GRF_EINVAL,
                 "grf_dense_steps_grad: bad arguments");
+    GRF_REQUIRE_IDS(n, "grf_dense_steps_grad", "n");
     hipStream_t st = S(stream);
     if (n == 0) {
         GRF_CHECK_HIP(hipMemsetAsync(grad, 0, (size_t)L * sizeof(double), st));

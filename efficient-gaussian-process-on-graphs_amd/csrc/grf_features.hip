@@ -269,6 +269,7 @@ int32_t grf_csr_row_lengths(int64_t n_sel, const int64_t *ptr, const int32_t *ro
                             grf_stream_t stream) {
     GRF_REQUIRE(n_sel >= 0 && ptr && (len || n_sel == 0), GRF_EINVAL, "grf_csr_row_lengths: bad arguments");
     if (n_sel == 0) return GRF_OK;
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n_sel, 256), 256, "csr_row_lengths_kernel");
     csr_row_lengths_kernel<<<(unsigned)cdiv<int64_t>(n_sel, 256), 256, 0, S(stream)>>>(n_sel, ptr, row_map, len);
     GRF_CHECK_LAUNCH("csr_row_lengths_kernel");
     return GRF_OK;
@@ -312,9 +313,9 @@ int32_t grf_csr_rows_dot_cols(int64_t n_sel, const int64_t *ptr, const int32_t *
 
 int32_t grf_dense_to_csr_count(int64_t n_rows, int64_t n_cols, const float *K, int64_t ldk, int32_t *cnt,
                                grf_stream_t stream) {
-    GRF_REQUIRE(n_rows >= 0 && n_cols >= 0 && n_cols < ((int64_t)1 << 31) && ldk >= n_cols &&
-                    (n_rows == 0 || (K && cnt)),
-                GRF_EINVAL, "grf_dense_to_csr_count: bad arguments");
+    GRF_REQUIRE(n_rows >= 0 && n_cols >= 0 && ldk >= n_cols && (n_rows == 0 || (K && cnt)), GRF_EINVAL,
+                "grf_dense_to_csr_count: bad arguments");
+    GRF_REQUIRE_IDS(n_cols, "grf_dense_to_csr_count", "n_cols");
     if (n_rows == 0) return GRF_OK;
     GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "dense_to_csr_kernel");
     dense_to_csr_kernel<false><<<(unsigned)cdiv<int64_t>(n_rows, 4), 256, 0, S(stream)>>>(n_rows, n_cols, K, ldk, cnt,
@@ -325,9 +326,9 @@ int32_t grf_dense_to_csr_count(int64_t n_rows, int64_t n_cols, const float *K, i
 
 int32_t grf_dense_to_csr_fill(int64_t n_rows, int64_t n_cols, const float *K, int64_t ldk, const int64_t *out_ptr,
                               int32_t *out_idx, double *out_val, grf_stream_t stream) {
-    GRF_REQUIRE(n_rows >= 0 && n_cols >= 0 && n_cols < ((int64_t)1 << 31) && ldk >= n_cols &&
-                    (n_rows == 0 || (K && out_ptr && out_idx && out_val)),
+    GRF_REQUIRE(n_rows >= 0 && n_cols >= 0 && ldk >= n_cols && (n_rows == 0 || (K && out_ptr && out_idx && out_val)),
                 GRF_EINVAL, "grf_dense_to_csr_fill: bad arguments");
+    GRF_REQUIRE_IDS(n_cols, "grf_dense_to_csr_fill", "n_cols");
     if (n_rows == 0) return GRF_OK;
     GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "dense_to_csr_kernel");
     dense_to_csr_kernel<true><<<(unsigned)cdiv<int64_t>(n_rows, 4), 256, 0, S(stream)>>>(

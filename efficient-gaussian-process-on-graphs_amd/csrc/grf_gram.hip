@@ -955,8 +955,10 @@ struct GramArgs {
 // One argument check for the row, sym, upper, kslice and cols entries (fn: the entry's name; args_ok: its own
 // pointer and range conditions; ld_min: the columns a K row holds).
 static int32_t gram_check(const char *fn, bool args_ok, int32_t unit, const void *t_rec, int64_t ldk, int64_t ld_min,
-                          int64_t band_width) {
+                          int64_t band_width, int64_t n_cols) {
     GRF_REQUIRE(args_ok, GRF_EINVAL, "%s: bad arguments", fn);
+    GRF_REQUIRE_IDS(n_cols, fn, "the column count");  // (the tiles hold rows and columns in int32)
+    GRF_REQUIRE_IDS(ld_min, fn, "the row count");
     GRF_REQUIRE(unit == GRF_REC_LINE || unit == GRF_REC_PACKED || unit == GRF_REC_SLOT, GRF_EINVAL,
                 "%s: rec_unit must be GRF_REC_LINE, GRF_REC_PACKED or GRF_REC_SLOT", fn);
     GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL, "%s: t_rec must be 128-byte aligned", fn);
@@ -1053,7 +1055,7 @@ static int32_t gram_sparse_rows_impl(const char *fn, int32_t rec_kind, int64_t n
     int32_t rc = gram_check(fn,
                             n_total >= 0 && 0 <= row_begin && row_begin <= row_end && row_end <= n_total && ptr &&
                                 t_desc && K && t_rowshift && t_rec,
-                            rec_unit, t_rec, ldk, n_total, band_width);
+                            rec_unit, t_rec, ldk, n_total, band_width, n_total);
     if (rc != GRF_OK) return rc;
     GRF_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= n_total, GRF_EINVAL, "%s: bad column slice [%lld, %lld)",
                 fn, (long long)k_begin, (long long)k_end);
@@ -1088,7 +1090,7 @@ static int32_t gram_sparse_upper_impl(const char *fn, int32_t rec_kind, int64_t 
                                       const int32_t *row_cuts, float *K, int64_t ldk, int32_t part_begin,
                                       int32_t part_end, int32_t n_parts, bool add_k, grf_stream_t stream) {
     int32_t rc = gram_check(fn, n_total >= 0 && ptr && t_desc && K && t_rowshift && t_rec, rec_unit, t_rec, ldk,
-                            n_total, band_width);
+                            n_total, band_width, n_total);
     if (rc != GRF_OK) return rc;
     GRF_REQUIRE(n_parts >= 1 && 0 <= part_begin && part_begin <= part_end && part_end <= n_parts, GRF_EINVAL,
                 "%s: bad tile parts [%d, %d) of %d", fn, part_begin, part_end, n_parts);
@@ -1186,14 +1188,15 @@ int32_t grf_gram_row_cuts(int64_t n_rows, const int64_t *ptr, const int32_t *idx
     GRF_REQUIRE(n_rows >= 0 && n_bands >= 0 && n_cols >= 0 &&
                     (n_rows == 0 || (ptr && idx && t_desc && col_w && row_cuts)),
                 GRF_EINVAL, "grf_gram_row_cuts: bad arguments");
+    GRF_REQUIRE_IDS(n_cols, "grf_gram_row_cuts", "n_cols");
     if (n_rows == 0) return GRF_OK;
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "row_cuts_kernel");
     if (n_cols > 0) {
         GRF_REQUIRE_GRID(cdiv<int64_t>(n_cols, 256), 256, "col_pairs_kernel");
         col_pairs_kernel<<<(unsigned)cdiv<int64_t>(n_cols, 256), 256, 0, S(stream)>>>(
             n_bands, n_cols, reinterpret_cast<const uint2 *>(t_desc), col_w);
         GRF_CHECK_LAUNCH("col_pairs_kernel");
     }
-    GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "row_cuts_kernel");
     row_cuts_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 4), 256, 0, S(stream)>>>(n_rows, ptr, idx, col_w, row_cuts);
     GRF_CHECK_LAUNCH("row_cuts_kernel");
     return GRF_OK;
@@ -1235,6 +1238,7 @@ int32_t grf_transpose_drop_columns(int64_t n_bands, int64_t n_cols, uint32_t *t_
                                    int32_t n_drop, grf_stream_t stream) {
     GRF_REQUIRE(n_bands >= 0 && n_cols >= 0 && n_drop >= 0 && (n_drop == 0 || (t_desc && cols)), GRF_EINVAL,
                 "grf_transpose_drop_columns: bad arguments");
+    GRF_REQUIRE_IDS(n_cols, "grf_transpose_drop_columns", "n_cols");
     const int64_t work = n_bands * (int64_t)n_drop;
     if (work == 0) return GRF_OK;
     GRF_REQUIRE_GRID(cdiv<int64_t>(work, 256), 256, "transpose_drop_kernel");
@@ -1257,7 +1261,7 @@ static int32_t gram_sparse_cols_impl(const char *fn, int64_t n_cols, int64_t row
     int32_t rc = gram_check(fn,
                             n_cols > 0 && 0 <= row_begin && row_begin <= row_end && (ptr || pad_cnt) && idx && val &&
                                 row_shift && t_rows >= 0 && t_desc && t_rec && K,
-                            rec_unit, t_rec, ldk, t_rows, band_width);
+                            rec_unit, t_rec, ldk, t_rows, band_width, n_cols);
     if (rc != GRF_OK) return rc;
     GRF_REQUIRE(sym_row0 < 0 || (row_begin <= sym_row0 && sym_row0 + t_rows <= row_end), GRF_EINVAL,
                 "%s: the symmetric square [sym_row0, sym_row0 + t_rows) must lie in the rows", fn);
@@ -1350,8 +1354,8 @@ int32_t grf_densify(int64_t n_rows, const int64_t *ptr, const int32_t *idx, cons
                     int64_t lda, grf_stream_t stream) {
     GRF_REQUIRE(n_rows >= 0 && ptr && out && lda >= 0, GRF_EINVAL, "grf_densify: bad arguments");
     if (n_rows == 0) return GRF_OK;
-    GRF_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)n_rows * (size_t)lda * sizeof(float), S(stream)));
     GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "densify_kernel");
+    GRF_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)n_rows * (size_t)lda * sizeof(float), S(stream)));
     densify_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 4), 256, 0, S(stream)>>>(n_rows, ptr, idx, val, out, lda);
     GRF_CHECK_LAUNCH("densify_kernel");
     return GRF_OK;

@@ -1197,6 +1197,8 @@ int32_t dense_args(const char *entry, int64_t n, int64_t k_dim, float *K, int64_
 int32_t dense_args_fp32(const char *entry, int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K,
                         int64_t ldk, bool upper_only, DenseArgs &a) {
     GRF_REQUIRE(n >= 0 && k_dim >= 0 && A && K && ldk >= n && lda >= k_dim, GRF_EINVAL, "%s: bad arguments", entry);
+    GRF_REQUIRE_IDS(n, entry, "n");
+    GRF_REQUIRE_IDS(k_dim, entry, "k_dim");
     GRF_REQUIRE(lda % 16 == 0 && ((uintptr_t)A & 15) == 0, GRF_EINVAL,
                 "%s: lda must be a multiple of 16 and A 16-byte aligned", entry);
     const int32_t rc = dense_args(entry, n, k_dim, K, ldk, upper_only, a);
@@ -1231,9 +1233,29 @@ void apply_plan(DenseArgs &a, const SkPlan &q, void *workspace) {
     a.xcd_slots = q.xcd_slots;
 }
 
+// The size functions' slab counts: bounds of the plans' (dense_plan: every tile in <= min(4, k-tiles) pieces and at
+// most one piece per slot below 2 kCUs tiles, then a tail of < 2 * 2 kCUs tiles in <= 3 pieces; sk_plan: two slabs per
+// slot; sk_plan_wide: two double slabs per CU) written in the tile and k-tile counts alone, so that they grow with n
+// and with k_dim -- the realised grids, cdiv(total, cdiv(total, slots)), do not, and a caller who sizes one
+// workspace for its largest problem must be able to reuse it for every smaller one.
+static int64_t dense_ws_slabs(int64_t n, int64_t k_dim, bool wide) {
+    const int64_t nt = cdiv<int64_t>(n, kTile), tiles = nt * (nt + 1) / 2, kt = cdiv<int64_t>(k_dim, kBK);
+    constexpr int64_t slots = 2 * kCUs;
+    const int64_t units = std::max<int64_t>(tiles * kt, 1);
+    const int64_t per_tile = tiles < slots ? std::min<int64_t>(tiles * std::min<int64_t>(4, kt), slots)
+                                           : (2 * slots - 1) * std::min<int64_t>(3, kt);
+    const int64_t stream_k = 2 * std::min<int64_t>(slots, units);
+    const int64_t wide_k = wide ? 4 * std::min<int64_t>(kCUs, units) : 0;
+    return std::max(per_tile, std::max(stream_k, wide_k));
+}
+static size_t dense_ws_bound(int64_t n, int64_t k_dim, bool wide) {
+    return kTicketBytes + (size_t)dense_ws_slabs(n, k_dim, wide) * kTile * kTile * sizeof(float);
+}
+
 size_t dense_gram_workspace_bytes(int64_t n, int64_t k_dim) {
     if (n <= 0) return 16;
-    return std::max<size_t>(16, std::max(dense_plan(n, k_dim).ws_bytes, sk_plan(n, k_dim).ws_bytes));
+    // (max with the plans themselves: the bound must never be short of what a launch takes)
+    return std::max(dense_ws_bound(n, k_dim, false), std::max(dense_plan(n, k_dim).ws_bytes, sk_plan(n, k_dim).ws_bytes));
 }
 
 // The MFMA Gram: tiles on and above the diagonal written to both triangles (upper_only: the tiles' K[row][col]
@@ -1276,7 +1298,7 @@ int32_t dense_gram(int64_t n, int64_t k_dim, const float *A, int64_t lda, float 
 // The split path: the fp32 path's workspace (tickets and slabs; the ticket block must be zero on first use)
 size_t dense_gram_split_workspace_bytes(int64_t n, int64_t k_dim) {
     const size_t base = dense_gram_workspace_bytes(n, k_dim);
-    return n <= 0 ? base : std::max(base, sk_plan_wide(n, k_dim).ws_bytes);
+    return n <= 0 ? base : std::max(std::max(base, dense_ws_bound(n, k_dim, true)), sk_plan_wide(n, k_dim).ws_bytes);
 }
 
 // The same K on the bf16 matrix cores: A split exactly into three bf16 planes, six products per term.
@@ -1324,7 +1346,9 @@ using namespace grf;
 extern "C" {
 #pragma GCC visibility push(default)
 
-size_t grf_gram_dense_workspace_bytes(int64_t n, int64_t k_dim) { return dense_gram_workspace_bytes(n, k_dim); }
+size_t grf_gram_dense_workspace_bytes(int64_t n, int64_t k_dim) {
+    return n > kMaxIds || k_dim > kMaxIds ? kSizeSaturated : dense_gram_workspace_bytes(n, k_dim);
+}
 
 int32_t grf_gram_dense_ws(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
                           void *workspace, size_t workspace_bytes, grf_stream_t stream) {
@@ -1342,7 +1366,7 @@ int32_t grf_gram_dense(int64_t n, int64_t k_dim, const float *A, int64_t lda, fl
 }
 
 size_t grf_gram_dense_split_workspace_bytes(int64_t n, int64_t k_dim) {
-    return dense_gram_split_workspace_bytes(n, k_dim);
+    return n > kMaxIds || k_dim > kMaxIds ? kSizeSaturated : dense_gram_split_workspace_bytes(n, k_dim);
 }
 
 int32_t grf_gram_dense_split(int64_t n, int64_t k_dim, const float *A, int64_t lda, float *K, int64_t ldk,
@@ -1358,7 +1382,10 @@ int32_t grf_gram_dense_split_upper(int64_t n, int64_t k_dim, const float *A, int
 }
 
 // ---- the planes path
-int64_t grf_planes_row_bytes(int64_t k_dim) { return cdiv<int64_t>(k_dim, kBK) * kPlaneBytes; }
+int64_t grf_planes_row_bytes(int64_t k_dim) {
+    if (k_dim <= 0) return 0;
+    return k_dim > kMaxIds ? kBoundSaturated : cdiv<int64_t>(k_dim, kBK) * kPlaneBytes;
+}
 
 int32_t grf_split_planes(int64_t n, int64_t k_dim, const float *A, int64_t lda, void *P, int64_t ldp,
                          grf_stream_t stream) {
@@ -1401,6 +1428,8 @@ int32_t grf_densify_padded_planes(int64_t n_rows, int64_t cap, int64_t n_cols, c
 int32_t grf_gram_dense_planes(int64_t n, int64_t k_dim, const void *P, int64_t ldp, float *K, int64_t ldk,
                               void *workspace, size_t workspace_bytes, grf_stream_t stream) {
     GRF_REQUIRE(n >= 0 && k_dim >= 0 && K && ldk >= n && (n == 0 || P), GRF_EINVAL, "grf_gram_dense_planes: bad arguments");
+    GRF_REQUIRE_IDS(n, "grf_gram_dense_planes", "n");
+    GRF_REQUIRE_IDS(k_dim, "grf_gram_dense_planes", "k_dim");
     GRF_REQUIRE(ldp >= grf_planes_row_bytes(k_dim) && ldp % 16 == 0 && ((uintptr_t)P & 15) == 0, GRF_EINVAL,
                 "grf_gram_dense_planes: ldp must cover the k-tiles' planes, a multiple of 16, P 16-byte aligned");
     DenseArgs a{};

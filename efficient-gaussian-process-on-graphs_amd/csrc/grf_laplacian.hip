@@ -922,27 +922,29 @@ using namespace grf;
 extern "C" {
 #pragma GCC visibility push(default)
 
-size_t grf_laplacian_csr_workspace_bytes(int64_t n) { return LapCsrWs(n).bytes; }
+size_t grf_laplacian_csr_workspace_bytes(int64_t n) { return n > kMaxIds ? kSizeSaturated : LapCsrWs(n).bytes; }
 
-size_t grf_laplacian_dense_workspace_bytes(int64_t n) { return LapDenseWs(n).bytes; }
+size_t grf_laplacian_dense_workspace_bytes(int64_t n) { return n > kMaxIds ? kSizeSaturated : LapDenseWs(n).bytes; }
 
 int32_t grf_laplacian_csr(int64_t n, const int64_t *a_ptr, const int32_t *a_idx, const double *a_val, int32_t mode,
                           int64_t *l_ptr, int32_t *l_idx, double *l_val, int64_t l_cap, double *deg, double *dinv,
                           void *workspace, size_t workspace_bytes, grf_stream_t stream) {
-    GRF_REQUIRE(n >= 0 && a_ptr && l_ptr && deg && dinv, GRF_EINVAL, "grf_laplacian_csr: bad arguments");
+    // (a_idx / a_val / l_idx / l_val may be NULL when there are no entries)
+    GRF_REQUIRE(n >= 0 && l_cap >= 0 && a_ptr && l_ptr && deg && dinv, GRF_EINVAL, "grf_laplacian_csr: bad arguments");
     GRF_REQUIRE(mode == GRF_LAP_SCIPY, GRF_EUNSUPPORTED,
                 "grf_laplacian_csr: only GRF_LAP_SCIPY is defined for CSR input (got %d)", mode);
+    GRF_REQUIRE_IDS(n, "grf_laplacian_csr", "n");
     const LapCsrWs L(n);
-    GRF_REQUIRE(workspace_bytes >= L.bytes, GRF_EINVAL, "grf_laplacian_csr: workspace too small (%zu < %zu)",
-                workspace_bytes, L.bytes);
+    GRF_REQUIRE(workspace && workspace_bytes >= L.bytes, GRF_EINVAL,
+                "grf_laplacian_csr: workspace too small (%zu < %zu)", workspace_bytes, L.bytes);
     hipStream_t st = S(stream);
     int32_t *cnt = (int32_t *)workspace;
     if (n == 0) {
         GRF_CHECK_HIP(hipMemsetAsync(l_ptr, 0, sizeof(int64_t), st));
         return GRF_OK;
     }
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n, 32), 256, "lap_deg_group_kernel");
     const unsigned gw = (unsigned)cdiv<int64_t>(n, 32);  // eight rows per wave
-    GRF_REQUIRE_GRID(gw, 256, "lap_deg_group_kernel");
     lap_deg_group_kernel<<<gw, 256, 0, st>>>(n, a_ptr, a_val, deg, dinv);
     GRF_CHECK_LAUNCH("lap_deg_group_kernel");
     lap_row_group_kernel<false><<<gw, 256, 0, st>>>(n, a_ptr, a_idx, a_val, deg, dinv, cnt, nullptr, nullptr, nullptr,
@@ -958,14 +960,15 @@ int32_t grf_laplacian_csr(int64_t n, const int64_t *a_ptr, const int32_t *a_idx,
 
 int32_t grf_laplacian_dense(int64_t n, const double *W, int32_t mode, int64_t *l_ptr, int32_t *l_idx, double *l_val,
                             int64_t l_cap, double *deg, void *workspace, size_t workspace_bytes, grf_stream_t stream) {
-    GRF_REQUIRE(n >= 0 && W && l_ptr && deg, GRF_EINVAL, "grf_laplacian_dense: bad arguments");
+    // (l_idx / l_val may be NULL when there are no entries)
+    GRF_REQUIRE(n >= 0 && l_cap >= 0 && W && l_ptr && deg, GRF_EINVAL, "grf_laplacian_dense: bad arguments");
     GRF_REQUIRE(mode == GRF_LAP_NUMPY || mode == GRF_LAP_NUMPY_SAFE || mode == GRF_LAP_COMBINATORIAL ||
                     mode == GRF_LAP_NONE,
                 GRF_EINVAL, "grf_laplacian_dense: bad mode %d", mode);
     GRF_REQUIRE(((uintptr_t)W & 7) == 0, GRF_EINVAL, "grf_laplacian_dense: W must be 8-byte aligned");
-    GRF_REQUIRE(n < INT32_MAX, GRF_EINVAL, "grf_laplacian_dense: n must fit int32 column indices");
+    GRF_REQUIRE(n < INT32_MAX, GRF_EUNSUPPORTED, "grf_laplacian_dense: n must fit int32 column indices");
     const LapDenseWs L(n);
-    GRF_REQUIRE(workspace_bytes >= L.bytes && ((uintptr_t)workspace & 255) == 0, GRF_EINVAL,
+    GRF_REQUIRE(workspace && workspace_bytes >= L.bytes && ((uintptr_t)workspace & 255) == 0, GRF_EINVAL,
                 "grf_laplacian_dense: workspace too small or not 256-byte aligned");
     hipStream_t st = S(stream);
     if (n == 0) {
@@ -981,8 +984,8 @@ int32_t grf_laplacian_dense(int64_t n, const double *W, int32_t mode, int64_t *l
     PwPlan<kPwPlanLeaves> plan;
     PwFrame frames[kPwDepth];
     if (!pw_plan_build(n, plan, frames)) plan.nl = 0;
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n, 4), 256, "lapd_stage_kernel");
     const unsigned g = (unsigned)cdiv<int64_t>(n, 4);
-    GRF_REQUIRE_GRID(g, 256, "lapd_stage_kernel");
     lapd_stage_kernel<<<g, 256, 0, st>>>(n, W, mode, plan, deg, dinv, scnt, scol, sval, flags, ticket);
     GRF_CHECK_LAUNCH("lapd_stage_kernel");
     const unsigned gt = (unsigned)cdiv<int64_t>(n, kLapdTileRows);

@@ -989,11 +989,14 @@ int32_t grf_concat_segments(int32_t n_seg, int64_t stride, const void *src, cons
     return GRF_OK;
 }
 
-size_t grf_scan_workspace_bytes(int64_t n) { return scan_ws_bytes(n); }
+size_t grf_scan_workspace_bytes(int64_t n) { return n > kMaxEntries ? kSizeSaturated : scan_ws_bytes(n); }
 
 int32_t grf_scan_counts(int64_t n, const int32_t *cnt, int64_t *out_ptr, void *workspace, size_t workspace_bytes,
                         grf_stream_t stream) {
     GRF_REQUIRE(n >= 0 && cnt && out_ptr, GRF_EINVAL, "grf_scan_counts: bad arguments");
+    // (a scan of one tile needs no workspace: NULL with 0 bytes is fine there)
+    GRF_REQUIRE(workspace || scan_ws_bytes(n) == 0, GRF_EINVAL, "grf_scan_counts: workspace is NULL (%zu bytes needed)",
+                scan_ws_bytes(n));
     return scan_counts_i32(n, cnt, out_ptr, workspace, workspace_bytes, S(stream));
 }
 
@@ -1004,6 +1007,7 @@ int32_t grf_compact_rows(int64_t n_rows, int64_t cap, const int32_t *cnt, const 
                 "grf_compact_rows: bad arguments");
     GRF_REQUIRE(!out_val || in_val, GRF_EINVAL, "grf_compact_rows: out_val needs in_val");
     GRF_REQUIRE(!out_val32 || in_val32, GRF_EINVAL, "grf_compact_rows: out_val32 needs in_val32");
+    GRF_REQUIRE_IDS(n_rows, "grf_compact_rows", "n_rows");
     if (n_rows == 0) return GRF_OK;
     const int64_t nwg = cdiv<int64_t>(n_rows, 4 * kCompactRows);
     GRF_REQUIRE_GRID(nwg, 256, "compact_rows_kernel");
@@ -1064,6 +1068,8 @@ static int32_t tr_check(const char *who, bool args, int64_t n_rows, int64_t n_co
     GRF_REQUIRE(rec_unit == GRF_REC_LINE || rec_unit == GRF_REC_PACKED || (slot_ok && rec_unit == GRF_REC_SLOT),
                 GRF_EINVAL, "%s: rec_unit must be GRF_REC_LINE%s", who,
                 slot_ok ? ", GRF_REC_PACKED or GRF_REC_SLOT" : " or GRF_REC_PACKED");
+    GRF_REQUIRE_IDS(n_rows, who, "n_rows");
+    GRF_REQUIRE_IDS(n_cols, who, "n_cols");
     GRF_REQUIRE(rec_unit != GRF_REC_SLOT || !split, GRF_EUNSUPPORTED, "%s: GRF_REC_SLOT has no sub-band split", who);
     GRF_REQUIRE(!staged || band_width % 64 == 0, GRF_EUNSUPPORTED, "%s: band_width must be a multiple of 64", who);
     GRF_REQUIRE(((uintptr_t)t_rec & 127) == 0, GRF_EINVAL, "%s: t_rec must be 128-byte aligned", who);
@@ -1088,7 +1094,7 @@ static int32_t tr_bin_and_shifts(hipStream_t st, int64_t n_rows, int64_t n_cols,
                                  float *t_maxabs, int32_t *t_rowshift) {
     char *s = (char *)staging;
     const size_t lds = (size_t)kBinCap * 8 + (size_t)sg.nreg * 4 + (kBinRows + 1 + 8) * 4;
-    GRF_REQUIRE_GRID(sg.nwg, 256, "tr_bin_kernel");
+    GRF_REQUIRE_GRID(sg.nwg, 256, "tr_bin_kernel");  // (the helper's own; its callers check it before their first memset)
     tr_bin_kernel<<<(unsigned)sg.nwg, 256, lds, st>>>(n_rows, n_cols, band_width, sg.cr, (int32_t)sg.nreg, ptr, idx, val,
                                                      (uint2 *)s, (int32_t *)(s + sg.tab), (float *)(s + sg.wg_max),
                                                      row_max, (double *)(s + sg.row_sum));
@@ -1097,7 +1103,10 @@ static int32_t tr_bin_and_shifts(hipStream_t st, int64_t n_rows, int64_t n_cols,
                              (const double *)(s + sg.row_sum), t_maxabs, t_rowshift);
 }
 
-size_t grf_transpose_workspace_bytes(int64_t n_buckets) { return TrPlanWs(n_buckets).bytes; }
+size_t grf_transpose_workspace_bytes(int64_t n_buckets) {
+    if (n_buckets > kMaxEntries) return kSizeSaturated;
+    return TrPlanWs(n_buckets > 0 ? n_buckets : 0).bytes;
+}
 
 int32_t grf_transpose_banded_plan(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
                                   const int64_t *ptr, const int32_t *idx, uint32_t *t_desc, int32_t counted,
@@ -1107,13 +1116,14 @@ int32_t grf_transpose_banded_plan(int64_t n_rows, int64_t n_cols, int64_t band_w
     if (rc != GRF_OK) return rc;
     const int64_t nb = cdiv<int64_t>(n_rows, band_width), nbk = nb * n_cols;
     const TrPlanWs ws(nbk);
-    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_plan: workspace too small (%zu < %zu)",
-                workspace_bytes, ws.bytes);
+    GRF_REQUIRE(workspace && workspace_bytes >= ws.bytes, GRF_EINVAL,
+                "grf_transpose_banded_plan: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
+    if (n_rows > 0 && !counted) GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "tr_count_kernel");
+    GRF_REQUIRE_GRID(cdiv<int64_t>(nbk, kScanTile), kScanThreads, "scan_reduce_kernel");  // (the scan over the buckets)
     hipStream_t st = S(stream);
     int32_t *cnt = (int32_t *)workspace;
     if (!counted) GRF_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)nbk * sizeof(int32_t), st));
     if (n_rows > 0 && !counted) {
-        GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "tr_count_kernel");
         tr_count_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 4), 256, 0, st>>>(n_rows, n_cols, band_width, ptr, idx,
                                                                           cnt);
         GRF_CHECK_LAUNCH("tr_count_kernel");
@@ -1133,7 +1143,9 @@ int32_t grf_transpose_banded_fill(int64_t n_rows, int64_t n_cols, int64_t band_w
     if (rc != GRF_OK) return rc;
     const int64_t nb = cdiv<int64_t>(n_rows, band_width), nbk = nb * n_cols;
     const TrPlanWs ws(nbk);
-    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_fill: workspace too small");
+    GRF_REQUIRE(workspace && workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_fill: workspace too small");
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "tr_fill_kernel");
+    GRF_REQUIRE_GRID(cdiv<int64_t>(nbk, 256), 256, "tr_pad_fill_kernel");
     hipStream_t st = S(stream);
     char *w = (char *)workspace;
     int32_t *cursor = (int32_t *)w;
@@ -1143,17 +1155,15 @@ int32_t grf_transpose_banded_fill(int64_t n_rows, int64_t n_cols, int64_t band_w
     GRF_CHECK_HIP(hipMemsetAsync(cursor, 0, (size_t)nbk * sizeof(int32_t), st));
     GRF_CHECK_HIP(hipMemsetAsync(t_maxabs, 0, sizeof(float), st));
     if (n_rows > 0) {
-        GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "tr_fill_kernel");
         tr_fill_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 4), 256, 0, st>>>(
             n_rows, n_cols, band_width, ptr, idx, val, desc, cursor, (unsigned char *)t_rec, rec_unit,
             reinterpret_cast<unsigned int *>(t_maxabs), row_max, row_sum);
         GRF_CHECK_LAUNCH("tr_fill_kernel");
-        GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 256), 256, "tr_rowshift_kernel");
         tr_rowshift_kernel<<<(unsigned)cdiv<int64_t>(n_rows, 256), 256, 0, st>>>(n_rows, row_max, row_sum, t_maxabs,
                                                                                 t_rowshift);
         GRF_CHECK_LAUNCH("tr_rowshift_kernel");
     }
-    GRF_REQUIRE_GRID(cdiv<int64_t>(nbk, 256), 256, "tr_pad_fill_kernel");
+    if (nbk == 0) return GRF_OK;  // (no rows: no buckets)
     tr_pad_fill_kernel<<<(unsigned)cdiv<int64_t>(nbk, 256), 256, 0, st>>>(nbk, desc, cursor, (unsigned char *)t_rec,
                                                                           rec_unit);
     GRF_CHECK_LAUNCH("tr_pad_fill_kernel");
@@ -1162,7 +1172,8 @@ int32_t grf_transpose_banded_fill(int64_t n_rows, int64_t n_cols, int64_t band_w
 
 size_t grf_transpose_staging_bytes(int64_t n_rows, int64_t n_cols, int64_t band_width, int64_t nnz) {
     if (n_cols <= 0 || band_width <= 0) return 0;
-    return TrStaging(n_rows, n_cols, nnz).bytes;
+    if (n_rows > kMaxIds || n_cols > kMaxIds || nnz > kMaxEntries) return kSizeSaturated;
+    return TrStaging(n_rows, n_cols, nnz > 0 ? nnz : 0).bytes;
 }
 
 int32_t grf_transpose_banded_fill_staged(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
@@ -1176,10 +1187,14 @@ int32_t grf_transpose_banded_fill_staged(int64_t n_rows, int64_t n_cols, int64_t
     if (rc != GRF_OK) return rc;
     const int64_t nb = cdiv<int64_t>(n_rows, band_width), nbk = nb * n_cols;
     const TrPlanWs ws(nbk);
-    GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "grf_transpose_banded_fill_staged: workspace too small");
+    GRF_REQUIRE(workspace && workspace_bytes >= ws.bytes, GRF_EINVAL,
+                "grf_transpose_banded_fill_staged: workspace too small");
     const TrStaging sg(n_rows, n_cols, nnz);
-    GRF_REQUIRE(nnz >= 0 && staging_bytes >= sg.bytes, GRF_EINVAL,
+    GRF_REQUIRE(nnz >= 0 && nnz <= kMaxEntries && staging_bytes >= sg.bytes, GRF_EINVAL,
                 "grf_transpose_banded_fill_staged: staging too small (%zu < %zu)", staging_bytes, sg.bytes);
+    GRF_REQUIRE_GRID(sg.nwg, 256, "tr_bin_kernel");
+    GRF_REQUIRE_GRID(nb * sg.nreg, 256, "tr_place_kernel");
+    GRF_REQUIRE_GRID(cdiv<int64_t>(nbk, kScanTile), kScanThreads, "scan_reduce_kernel");  // (the scan over the buckets)
     hipStream_t st = S(stream);
     char *w = (char *)workspace;
     int32_t *cnt = (int32_t *)w;  // (the bucket counts from the plan)
@@ -1193,7 +1208,6 @@ int32_t grf_transpose_banded_fill_staged(int64_t n_rows, int64_t n_cols, int64_t
     if (rc != GRF_OK) return rc;
     const int64_t n_regions = nb * sg.nreg;
     const size_t lds2 = (size_t)8 * sg.cr + kPlaceCap;
-    GRF_REQUIRE_GRID(n_regions, 256, "tr_place_kernel");
     tr_place_kernel<<<(unsigned)n_regions, 256, lds2, st>>>(
         n_rows, n_cols, band_width, sg.cr, (int32_t)sg.nreg, ptr, reinterpret_cast<const uint2 *>(t_desc), ent_off,
         (const uint2 *)staging, (const int32_t *)((char *)staging + sg.tab), (unsigned char *)t_rec, rec_unit);
@@ -1203,12 +1217,15 @@ int32_t grf_transpose_banded_fill_staged(int64_t n_rows, int64_t n_cols, int64_t
 
 size_t grf_transpose_self_workspace_bytes(int64_t n_rows, int64_t n_cols, int64_t band_width) {
     if (n_cols <= 0 || band_width <= 0) return 16;
+    if (n_rows > kMaxIds || n_cols > kMaxIds) return kSizeSaturated;
     return TrSelfWs(n_rows, n_cols, band_width).bytes;
 }
 
 int64_t grf_transpose_self_units_bound(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
                                        int64_t nnz) {
     if (n_cols <= 0 || band_width <= 0) return 1;
+    if (n_rows > kMaxIds || n_cols > kMaxIds || nnz > kMaxEntries) return kBoundSaturated;
+    if (nnz < 0) nnz = 0;
     const int64_t nb = cdiv<int64_t>(std::max<int64_t>(n_rows, 1), band_width), nbk = nb * n_cols;
     const int64_t n_regions = TrSelfWs(n_rows, n_cols, band_width).n_regions;
     // the sum of tr_region_units over the regions, for any split of nnz entries
@@ -1220,6 +1237,8 @@ int64_t grf_transpose_self_units_bound(int64_t n_rows, int64_t n_cols, int64_t b
 
 int64_t grf_transpose_self_triples_lines_bound(int64_t n_rows, int64_t n_cols, int64_t band_width, int64_t nnz) {
     if (n_cols <= 0 || band_width <= 0) return 1;
+    if (n_rows > kMaxIds || n_cols > kMaxIds || nnz > kMaxEntries) return kBoundSaturated;
+    if (nnz < 0) nnz = 0;
     const int64_t nb = cdiv<int64_t>(std::max<int64_t>(n_rows, 1), band_width), nbk = nb * n_cols;
     // the sum of tr_triple_lines_bound over the regions, for any split of nnz entries
     return tr_triple_lines_bound(nnz, nbk) + TrSelfWs(n_rows, n_cols, band_width).n_regions;
@@ -1242,7 +1261,7 @@ static int32_t transpose_banded_self(const char *who, int32_t rec_kind, int64_t 
     const TrSelfWs ws(n_rows, n_cols, band_width);
     GRF_REQUIRE(workspace_bytes >= ws.bytes, GRF_EINVAL, "%s: workspace too small", who);
     const TrStaging sg(n_rows, n_cols, nnz);
-    GRF_REQUIRE(nnz >= 0 && staging_bytes >= sg.bytes, GRF_EINVAL, "%s: staging too small", who);
+    GRF_REQUIRE(nnz >= 0 && nnz <= kMaxEntries && staging_bytes >= sg.bytes, GRF_EINVAL, "%s: staging too small", who);
     const int64_t units_bound = triples ? grf_transpose_self_triples_lines_bound(n_rows, n_cols, band_width, nnz)
                                         : grf_transpose_self_units_bound(n_rows, n_cols, band_width, rec_unit, nnz);
     GRF_REQUIRE(t_rec_bytes >= units_bound * rec_unit, GRF_ECAPACITY, "%s: t_rec too small for the region slabs", who);
@@ -1250,6 +1269,12 @@ static int32_t transpose_banded_self(const char *who, int32_t rec_kind, int64_t 
     const size_t lds_tri = (size_t)sg.cr * (kTriBlocks * (sizeof(TriBlock) + 4) + 4) + 32 + kPlaceCap;
     GRF_REQUIRE(!triples || lds_tri <= 160 * 1024, GRF_EUNSUPPORTED, "%s: regions of %d columns do not fit the LDS tables",
                 who, sg.cr);
+    GRF_REQUIRE(n_rows == 0 || ((uintptr_t)t_split & 15) == 0, GRF_EINVAL, "%s: t_split must be 16-byte aligned", who);
+    if (n_rows > 0) {  // (every launch below, checked before the first one)
+        GRF_REQUIRE_GRID(sg.nwg, 256, "tr_bin_kernel");
+        GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 256), 256, "tr_rowshift_kernel");
+        GRF_REQUIRE_GRID(ws.n_regions, 256, "tr_place_self_kernel");
+    }
     hipStream_t st = S(stream);
     uint2 *desc = reinterpret_cast<uint2 *>(t_desc);
     GRF_CHECK_HIP(hipMemsetAsync(t_maxabs, 0, sizeof(float), st));
@@ -1257,7 +1282,6 @@ static int32_t transpose_banded_self(const char *who, int32_t rec_kind, int64_t 
         GRF_CHECK_HIP(hipMemsetAsync(t_desc, 0, (size_t)(nbk + 1) * 8, st));
         return GRF_OK;
     }
-    GRF_REQUIRE(((uintptr_t)t_split & 15) == 0, GRF_EINVAL, "%s: t_split must be 16-byte aligned", who);
     char *w = (char *)workspace;
     int64_t *region_units = (int64_t *)(w + ws.region_units), *region_base = (int64_t *)(w + ws.region_base);
     const uint2 *ent = (const uint2 *)staging;
@@ -1277,7 +1301,6 @@ static int32_t transpose_banded_self(const char *who, int32_t rec_kind, int64_t 
     rc = scan_exclusive<int64_t>(n_regions, region_units, ScanIdentity{}, RegionBaseOut{region_base, desc + nbk},
                                  (int64_t *)(w + ws.scan), st);
     if (rc != GRF_OK) return rc;
-    GRF_REQUIRE_GRID(n_regions, 256, "tr_place_self_kernel");
     if (triples) {
         tr_place_self_triples_kernel<<<(unsigned)n_regions, 256, lds_tri, st>>>(
             n_rows, n_cols, band_width, cr, nreg, ptr, region_base, ent, tab, desc, (unsigned char *)t_rec);
@@ -1334,6 +1357,7 @@ int32_t grf_transpose_banded_self_rec(int32_t rec_kind, int64_t n_rows, int64_t 
 }
 
 size_t grf_phi_row_shifts_workspace_bytes(int64_t n_rows) {
+    if (n_rows > kMaxIds) return kSizeSaturated;
     const int64_t n = std::max<int64_t>(n_rows, 1);
     return tr_align((size_t)n * 4) + tr_align((size_t)n * 8) + tr_align((size_t)cdiv<int64_t>(n, 4) * 4);
 }
@@ -1352,6 +1376,7 @@ int32_t grf_compact_rows_stats(int64_t n_rows, int64_t cap, const int32_t *cnt, 
     GRF_REQUIRE(n_rows >= 0 && cap >= 0 && cnt && out_ptr && in_idx && out_idx && in_val32 && out_val32 && stats,
                 GRF_EINVAL, "grf_compact_rows_stats: bad arguments");
     GRF_REQUIRE(!out_val || in_val, GRF_EINVAL, "grf_compact_rows_stats: out_val needs in_val");
+    GRF_REQUIRE_IDS(n_rows, "grf_compact_rows_stats", "n_rows");
     GRF_REQUIRE(stats_bytes >= grf_phi_row_shifts_workspace_bytes(n_rows), GRF_EINVAL,
                 "grf_compact_rows_stats: stats buffer too small");
     if (n_rows == 0) return GRF_OK;
@@ -1369,6 +1394,8 @@ int32_t grf_compact_rows_stats(int64_t n_rows, int64_t cap, const int32_t *cnt, 
 int32_t grf_phi_row_shifts_stats(int64_t n_rows, const void *stats, float *maxabs, int32_t *row_shift,
                                  grf_stream_t stream) {
     GRF_REQUIRE(n_rows >= 0 && stats && maxabs && row_shift, GRF_EINVAL, "grf_phi_row_shifts_stats: bad arguments");
+    GRF_REQUIRE_IDS(n_rows, "grf_phi_row_shifts_stats", "n_rows");
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 256), 256, "tr_rowshift_kernel");
     hipStream_t st = S(stream);
     GRF_CHECK_HIP(hipMemsetAsync(maxabs, 0, sizeof(float), st));
     if (n_rows == 0) return GRF_OK;
@@ -1382,14 +1409,15 @@ int32_t grf_phi_row_shifts_stats(int64_t n_rows, const void *stats, float *maxab
 static int32_t phi_row_shifts(const char *who, int64_t n_rows, const int64_t *ptr, int64_t cap, const int32_t *cnt,
                               const float *val, float *maxabs, int32_t *row_shift, void *workspace,
                               size_t workspace_bytes, hipStream_t st) {
+    GRF_REQUIRE_IDS(n_rows, who, "n_rows");
     GRF_REQUIRE(workspace_bytes >= grf_phi_row_shifts_workspace_bytes(n_rows), GRF_EINVAL, "%s: workspace too small", who);
+    GRF_REQUIRE_GRID(cdiv<int64_t>(n_rows, 4), 256, "phi_row_stats_kernel");
     GRF_CHECK_HIP(hipMemsetAsync(maxabs, 0, sizeof(float), st));
     if (n_rows == 0) return GRF_OK;
     float *row_max, *wg_max;
     double *row_sum;
     row_stats_layout(workspace, n_rows, row_max, row_sum, wg_max);
     const int64_t nwg = cdiv<int64_t>(n_rows, 4);
-    GRF_REQUIRE_GRID(nwg, 256, "phi_row_stats_kernel");
     phi_row_stats_kernel<<<(unsigned)nwg, 256, 0, st>>>(n_rows, ptr, val, wg_max, row_max, row_sum, cap, cnt);
     GRF_CHECK_LAUNCH("phi_row_stats_kernel");
     return row_shifts_finish(st, n_rows, nwg, wg_max, row_max, row_sum, maxabs, row_shift);

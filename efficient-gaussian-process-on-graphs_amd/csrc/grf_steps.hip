@@ -602,12 +602,15 @@ int32_t grf_walk_phi(int64_t n, const int64_t *g_ptr, const int32_t *g_idx, cons
                             phi_idx, phi_val, phi_val32, t_count, band_width, n, S(stream), count_row0);
 }
 
-size_t grf_walk_aug_bytes(int64_t nnz) { return kAugHeader + (size_t)(nnz > 0 ? nnz : 0) * sizeof(AugRec); }
+size_t grf_walk_aug_bytes(int64_t nnz) {
+    return nnz > kMaxEntries ? kSizeSaturated : kAugHeader + (size_t)(nnz > 0 ? nnz : 0) * sizeof(AugRec);
+}
 
 int32_t grf_walk_aug(int64_t n, const int64_t *g_ptr, const int32_t *g_idx, const double *g_val, void *g_aug,
                      grf_stream_t stream) {
     GRF_REQUIRE(n >= 0 && g_ptr && g_idx && g_val && g_aug, GRF_EINVAL, "grf_walk_aug: bad arguments");
     GRF_REQUIRE(((uintptr_t)g_aug & 31) == 0, GRF_EINVAL, "grf_walk_aug: g_aug must be 32-byte aligned");
+    GRF_REQUIRE_IDS(n, "grf_walk_aug", "n");
     if (n == 0) return GRF_OK;
     // GRF_WALK_AUG16=0: always the 32-byte records (A/B; read per call so tests can cover both formats)
     const char *e16 = getenv("GRF_WALK_AUG16");
@@ -626,6 +629,7 @@ int32_t grf_steps_densify(int64_t n_src, int64_t m, int32_t L, int64_t n_cols, c
                           const int32_t *step_idx, const double *step_val, double *out, grf_stream_t stream) {
     GRF_REQUIRE(n_src >= 0 && m >= 1 && L >= 1 && n_cols >= 0 && step_cnt && step_idx && step_val && out,
                 GRF_EINVAL, "grf_steps_densify: bad arguments");
+    GRF_REQUIRE_IDS(n_cols, "grf_steps_densify", "n_cols");
     if (n_src == 0) return GRF_OK;
     GRF_REQUIRE_GRID(cdiv<int64_t>(n_src * L, 4), 256, "steps_densify_kernel");
     steps_densify_kernel<<<(unsigned)cdiv<int64_t>(n_src * L, 4), 256, 0, S(stream)>>>(n_src, m, L, n_cols, step_cnt,

@@ -9,6 +9,32 @@
  * Buffers whose size depends on the data are bounded by documented caps
  * (`*_cap` arguments) so that no entry point needs a host round trip.
  *
+ * Argument checks.  Every entry checks its arguments on the host before anything touches a device; a refused
+ * call launches nothing, writes nothing and leaves its reason in grf_last_error():
+ *   GRF_EINVAL        a negative size or capacity; a NULL pointer to an array of fixed size (row pointers of
+ *                     n + 1, per-row inputs and outputs, parameter structs, a workspace that is needed); a leading
+ *                     dimension below the width; a broken alignment rule (stated per entry: 8, 16, 32, 128 or 256
+ *                     bytes); a workspace that is NULL or shorter than its *_workspace_bytes; an enum or scalar
+ *                     out of range (p_halt outside [0, 1), walks_per_node < 1, NaN, a PCG64 source range that is
+ *                     not whole chunks, ...).
+ *   GRF_EUNSUPPORTED  a node, row or column count past the int32 ids the CSR arrays hold (> 2^31 - 1); a launch
+ *                     of 2^32 or more work-items (split the input); a band_width that is not a multiple of 64 in
+ *                     [64, 8192] where the entry bins by bands; a variant this build does not have.
+ *   GRF_ECAPACITY     a capacity the host can check is short (t_rec_bytes below the units bound).
+ * NULL when empty.  Arrays whose length depends on the data -- a CSR's idx / val, out_idx / out_val, t_idx /
+ * t_val, the records t_rec point at -- hold no element when there are no entries, and callers (the Python engine:
+ * the data pointer of an empty tensor) pass NULL for them then.  Entries that do not already insist on them must
+ * therefore not be given new NULL checks for these arrays; they are never read or written when empty.
+ * Size functions are pure host functions.  Those of the Laplacians, grf_walk_aug, the scan, the banded transposes
+ * (workspace, staging, units and lines bounds), grf_phi_row_shifts, the dense Grams (grf_gram_dense_workspace_bytes,
+ * grf_gram_dense_split_workspace_bytes, grf_planes_row_bytes), grf_dense_steps_grad and grf_csr_transpose are
+ * monotone in every argument over the sizes their entry accepts (a workspace sized for the largest problem serves
+ * every smaller one), count a negative size as 0, and saturate: an argument beyond the entry's domain -- a node /
+ * row / column count > 2^31 - 1, an entry or bucket count (nnz, n_buckets) > 2^40 -- or a product that would wrap
+ * gives SIZE_MAX (INT64_MAX for the int64 bounds), never a small wrapped value.  (The size functions of the CG,
+ * polynomial, SpGEMM, expm, posterior and steps_frob entries are specified with those entries and make no such
+ * promise beyond their entries' domains.)
+ *
  * The reference has no FFI: its boundary is a set of Python functions
  * (SURVEY.md §8b).  Each entry point below replaces the reference routine
  * cited next to it (paths relative to the reference checkout).
@@ -81,7 +107,7 @@ int32_t grf_version(void);
 /* number of HIP devices visible (0 if none); never fails */
 int32_t grf_device_count(void);
 /* select the device for subsequent calls on this host thread */
-int32_t grf_set_device(int32_t device);
+int32_t grf_set_device(int32_t device); /* device < 0: GRF_EINVAL */
 
 /* ------------------------------------------------------------------ Laplacian
  * Replaces efficient_graph_gp_sparse/utils_sparse/graph_utils.py:5-30
@@ -89,7 +115,14 @@ int32_t grf_set_device(int32_t device);
  * In : A (n x n CSR, canonical: sorted, no duplicates): a_ptr[n+1] (int64),
  *      a_idx[nnz] (int32), a_val[nnz] (float64).
  * Out: l_ptr[n+1], l_idx[l_cap], l_val[l_cap] with l_cap >= nnz(A) + n;
- *      deg[n], dinv[n] (float64, scratch + diagnostics).  Columns ascending. */
+ *      deg[n], dinv[n] (float64, scratch + diagnostics).  Columns ascending.
+ * n <= 2^31 - 1 (GRF_EUNSUPPORTED beyond); mode must be GRF_LAP_SCIPY (GRF_EUNSUPPORTED otherwise); workspace:
+ * grf_laplacian_csr_workspace_bytes(n) bytes, not NULL.  n == 0 writes l_ptr[0] = 0 and nothing else.
+ * Truncation rule (both Laplacians): l_cap is a data-dependent cap, so a short one is not an error the host can
+ * see.  l_ptr is always the FULL row pointer (l_ptr[n] = the entries the result has); an entry whose position is
+ * >= l_cap is not written (every store to l_idx / l_val is behind `position < l_cap`), so the words at and past
+ * l_cap are untouched and the entries below l_cap are the exact prefix of the full result.  The caller compares
+ * l_ptr[n] with l_cap. */
 int32_t grf_laplacian_csr(int64_t n, const int64_t *a_ptr, const int32_t *a_idx, const double *a_val, int32_t mode,
                           int64_t *l_ptr, int32_t *l_idx, double *l_val, int64_t l_cap, double *deg, double *dinv,
                           void *workspace, size_t workspace_bytes, grf_stream_t stream);
@@ -100,7 +133,9 @@ size_t grf_laplacian_csr_workspace_bytes(int64_t n);
  * efficient_graph_gp/preprocessing/laplacian_np.py:3-35 followed by the
  * neighbour scan np.flatnonzero(L[row]) of random_walk_samplers/sampler.py:22-28.
  * In : W dense row-major n x n float64.  mode: NUMPY / NUMPY_SAFE / COMBINATORIAL / NONE.
- * Out: the walk matrix as CSR of its nonzeros (ascending columns), l_cap >= nnz. */
+ * Out: the walk matrix as CSR of its nonzeros (ascending columns), l_cap >= nnz (truncation rule above).
+ * n < 2^31 - 1 (GRF_EUNSUPPORTED beyond); a mode other than the four is GRF_EINVAL; W 8-byte aligned; workspace:
+ * grf_laplacian_dense_workspace_bytes(n) bytes, 256-byte aligned, not NULL.  n == 0 writes l_ptr[0] = 0 only. */
 int32_t grf_laplacian_dense(int64_t n, const double *W, int32_t mode, int64_t *l_ptr, int32_t *l_idx, double *l_val,
                             int64_t l_cap, double *deg, void *workspace, size_t workspace_bytes, grf_stream_t stream);
 
@@ -120,7 +155,10 @@ size_t grf_laplacian_dense_workspace_bytes(int64_t n);
  *   continues on blocks (l, w, s, 1), (l, w, s, 2), ...; the L-th recorded visit draws nothing.
  * RNG GRF_RNG_PCG64 : chunks = np.array_split(arange(n), n_chunks); chunk c is one
  *   numpy default_rng(seed + c) stream; [src_begin, src_end) must be a union of
- *   whole chunks (use grf_chunk_bounds). */
+ *   whole chunks (use grf_chunk_bounds), n_chunks >= 1.
+ * Checked (GRF_EINVAL): params not NULL, walks_per_node in [1, 2^31), max_walk_length >= 1, p_halt in [0, 1) (a NaN
+ * is refused), load_rule and rng in their enums, 0 <= src_begin <= src_end <= n, g_aug 32-byte aligned; n <=
+ * 2^31 - 1 and (src_end - src_begin) * walks_per_node < 2^32 else GRF_EUNSUPPORTED.  No sources: nothing written. */
 typedef struct grf_walk_params {
     int64_t walks_per_node; /* m                     */
     double p_halt;          /* p                     */
@@ -150,14 +188,15 @@ int64_t grf_chunk_bounds(int64_t n, int64_t n_chunks, int64_t c);
  * sampler.py:137-146,188-203: for every (source, step) the distinct visited nodes
  * (ascending) with value = (sum of loads in walk order) normalised by `norm`.
  * Out (padded rows, row capacity m): step_cnt[ns*L], step_idx[ns*L*m],
- * step_val[ns*L*m] at row (s_local * L + l).  Explicit zeros are kept. */
+ * step_val[ns*L*m] at row (s_local * L + l).  Explicit zeros are kept.
+ * m in [1, 16384] (GRF_EUNSUPPORTED above), L >= 1, norm in its enum; n_src == 0 writes nothing. */
 int32_t grf_steps(int64_t n_src, int64_t m, int32_t L, int32_t norm, const int32_t *slot_node,
                   const double *slot_load, int32_t *step_cnt, int32_t *step_idx, double *step_val,
                   grf_stream_t stream);
 
 /* Dense (N, N, L) feature tensor of RandomWalk.get_random_walk_matrices
  * (sampler.py:188-203): out[(s * n_cols + j) * L + l] = step value; out must be
- * zero-filled by the caller. */
+ * zero-filled by the caller.  n_cols <= 2^31 - 1. */
 int32_t grf_steps_densify(int64_t n_src, int64_t m, int32_t L, int64_t n_cols, const int32_t *step_cnt,
                           const int32_t *step_idx, const double *step_val, double *out, grf_stream_t stream);
 
@@ -166,7 +205,9 @@ int32_t grf_steps_densify(int64_t n_src, int64_t m, int32_t L, int64_t n_cols, c
  * (Phi = sum_l f_l M_l, exact zeros dropped; steps l < min(n_f, L)).
  * From padded step rows (grf_steps output).  Out: padded Phi rows with capacity
  * phi_cap >= min(m * L, n): phi_cnt[ns], phi_idx[ns*phi_cap], phi_val[ns*phi_cap]
- * (float64), and optionally phi_val32 (float32 copy, may be NULL). */
+ * (float64), and optionally phi_val32 (float32 copy, may be NULL).
+ * L <= 64 (GRF_EUNSUPPORTED above); phi_cap >= 1; n_f >= 0 with f not NULL unless n_f == 0 (grf_phi_fused and
+ * grf_walk_phi alike).  A row longer than phi_cap is cut at phi_cap entries (phi_cnt holds what was written). */
 int32_t grf_phi(int64_t n_src, int64_t m, int32_t L, const int32_t *step_cnt, const int32_t *step_idx,
                 const double *step_val, const double *f, int32_t n_f, int64_t phi_cap, int32_t *phi_cnt,
                 int32_t *phi_idx, double *phi_val, float *phi_val32, grf_stream_t stream);
@@ -203,7 +244,8 @@ int32_t grf_phi_fused(int64_t n_src, int64_t m, int32_t L, int32_t norm, const i
                       int32_t *phi_idx, double *phi_val, float *phi_val32, grf_stream_t stream);
 
 /* --------------------------------------------------------- sparse utilities */
-/* exclusive scan of int32 counts -> int64 row pointers out[n+1] */
+/* exclusive scan of int32 counts -> int64 row pointers out[n+1] (n == 0: out[0] = 0).  workspace:
+ * grf_scan_workspace_bytes(n) bytes -- 0 up to one tile of 4096 counts, where NULL is accepted. */
 int32_t grf_scan_counts(int64_t n, const int32_t *cnt, int64_t *out_ptr, void *workspace, size_t workspace_bytes,
                         grf_stream_t stream);
 size_t grf_scan_workspace_bytes(int64_t n);
@@ -212,7 +254,8 @@ size_t grf_scan_workspace_bytes(int64_t n);
 int32_t grf_compact_rows(int64_t n_rows, int64_t cap, const int32_t *cnt, const int64_t *out_ptr,
                          const int32_t *in_idx, const double *in_val, const float *in_val32, int32_t *out_idx,
                          double *out_val, float *out_val32, grf_stream_t stream);
-/* grf_compact_rows (float values required) that also writes the rows' Gram shift statistics into
+/* (n_rows, cap >= 0; cnt, out_ptr, in_idx, out_idx not NULL; an output array needs its input array.)
+ * grf_compact_rows (float values required) that also writes the rows' Gram shift statistics into
  * `stats` (grf_phi_row_shifts_workspace_bytes(n_rows) bytes) for grf_phi_row_shifts_stats. */
 int32_t grf_compact_rows_stats(int64_t n_rows, int64_t cap, const int32_t *cnt, const int64_t *out_ptr,
                                const int32_t *in_idx, const double *in_val, const float *in_val32, int32_t *out_idx,
@@ -221,7 +264,8 @@ int32_t grf_compact_rows_stats(int64_t n_rows, int64_t cap, const int32_t *cnt, 
 
 /* dst[dst_off[r] + i] = src[r * stride + i] for i < seg_len[r], r < n_seg (4-byte elements; lengths
  * and offsets are device arrays): the compaction of a fixed-stride all-gather of n_seg ranks'
- * CSR segments (the multi-GPU Phi gather, grf_amd/dist.py) without reading any size back. */
+ * CSR segments (the multi-GPU Phi gather, grf_amd/dist.py) without reading any size back.
+ * n_seg in [0, 65535], stride >= 0; n_seg == 0 or stride == 0 touches nothing. */
 int32_t grf_concat_segments(int32_t n_seg, int64_t stride, const void *src, const int64_t *seg_len,
                             const int64_t *dst_off, void *dst, grf_stream_t stream);
 
@@ -237,8 +281,10 @@ int32_t grf_concat_segments(int32_t n_seg, int64_t stride, const void *src, cons
  *   fill: t_rec (>= total units * rec_unit bytes, 128-byte aligned), t_maxabs[1] = max |Phi| and
  *         t_rowshift[n_rows]: the Gram kernel's per-row fixed-point scale 2^shift (every term
  *         < 2^51, the row's sum of |terms| < 2^62).
- * workspace >= grf_transpose_workspace_bytes(n_bands * n_cols), shared by both calls.
- * band_width <= 8192. */
+ * workspace >= grf_transpose_workspace_bytes(n_bands * n_cols), shared by both calls (not NULL).
+ * band_width <= 8192; n_rows, n_cols <= 2^31 - 1, n_cols >= 1.  The launch sizes of a call's own kernels and of its
+ * first-level scan are checked before its first launch or memset, in all the transpose entries: a refused call has
+ * touched nothing. */
 int32_t grf_transpose_banded_plan(int64_t n_rows, int64_t n_cols, int64_t band_width, int32_t rec_unit,
                                   const int64_t *ptr, const int32_t *idx, uint32_t *t_desc, int32_t counted,
                                   void *workspace, size_t workspace_bytes, grf_stream_t stream);
@@ -565,7 +611,8 @@ int32_t grf_spmm_csr_f64(int64_t n_out, const int64_t *ptr, const int32_t *idx, 
 
 /* linear_cg(A._matmul, rhs, tolerance) with A = Phi_t Phi_t^T + noise I, Phi_t = Phi[row_map]
  * (n_sys rows; t_* its transpose from grf_csr_transpose): sparse_grf_model.py:34, 43.
- * rhs / x: [n_sys x ld] fp32, n_rhs in [1, 256] columns solved together.  Same rule as
+ * rhs / x: [n_sys x ld] fp32, n_rhs in [1, 256] columns solved together (GRF_EUNSUPPORTED outside); n_sys and
+ * n_cols >= 1, ld_rhs and ldx >= n_rhs, max_iter >= 0, a NaN noise is GRF_EINVAL (all the Gram solves).  Same rule as
  * linear_cg: per-column normalisation, eps = stop_updating_after = 1e-10, stop after
  * iteration k >= min(10, max_iter - 1) once the mean residual norm < tolerance.
  * *iters_out (host pointer, may be NULL) receives the iterations run and resid_out (host,

@@ -8,6 +8,8 @@ import re
 
 import expm_reference as R
 
+import abi_contract
+
 NEW = ["grf_gemm_nt_f64_workspace_bytes", "grf_gemm_nt_f64", "grf_expm_squarings", "grf_expm_sym_f64_workspace_bytes",
        "grf_expm_sym_f64"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,7 +70,7 @@ def test_squarings_agree_with_the_restatement():
 
 def test_argument_checks_need_no_device():
     from grf_amd import _lib
-    lib = _lib.load()
+    lib = abi_contract.device_less_lib()  # (made-up pointers: never in a process that sees a GPU)
     EINVAL, EUNSUP = _lib.GRF_EINVAL, _lib.GRF_EUNSUPPORTED
     a, b, c, w = (ctypes.c_void_p(1 << 20), ctypes.c_void_p(2 << 20), ctypes.c_void_p(3 << 20),
                   ctypes.c_void_p(4 << 20))  # (never dereferenced: every call below is refused)

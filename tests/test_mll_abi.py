@@ -3,6 +3,8 @@ companion): declared in the binding, exported by the built library, and checked 
 before anything touches a device."""
 import ctypes
 
+import abi_contract
+
 NEW = ["grf_cg_gram_solve_lanczos_f64", "grf_steps_frob_f64", "grf_steps_frob_workspace_bytes"]
 
 
@@ -17,11 +19,11 @@ def test_new_symbols_are_bound_and_exported():
 
 def test_steps_frob_argument_checks_need_no_device():
     from grf_amd import _lib
-    lib = _lib.load()
+    lib = abi_contract.device_less_lib()  # (made-up pointers: never in a process that sees a GPU)
     assert lib.grf_steps_frob_workspace_bytes(1, 1) >= 256 + 8
     assert lib.grf_steps_frob_workspace_bytes(1 << 20, 64) >= 256 + 64 * 8
     one = (ctypes.c_void_p * 1)(8)
-    p = ctypes.cast(one, ctypes.c_void_p)
+    p = one  # (a host array: the harness sends its bytes, not this process's address)
     d = ctypes.c_void_p(8)  # (never dereferenced: every call below is refused by its argument checks)
 
     def call(n_sel=4, L=1, ld=4, ldw=4, n_rhs=4, out=d, ws=d, ws_bytes=1 << 20):

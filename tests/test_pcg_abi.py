@@ -2,6 +2,8 @@
 exported by the built library, and checked for their arguments before anything touches a device."""
 import ctypes
 
+import abi_contract
+
 NEW = ["grf_gram_jacobi_f64", "grf_pcg_workspace_bytes", "grf_pcg_gram_solve_f64", "grf_pcg_gram_solve_lanczos_f64",
        "grf_pcg_poly_workspace_bytes", "grf_pcg_poly_solve_f64", "grf_pcg_poly_solve_lanczos_f64"]
 
@@ -49,7 +51,7 @@ def test_workspace_sizes_are_pinned():
 
 def test_messages_name_the_entry_that_was_called():
     from grf_amd import _lib
-    lib = _lib.load()
+    lib = abi_contract.device_less_lib()  # (made-up pointers: never in a process that sees a GPU)
     d = ctypes.c_void_p(8)  # (never dereferenced: a bad stride is refused before anything is read)
     tail = (0.1, d, 3, 4, 1.0, 5, d, 4, d, 1 << 40, None, None)   # ld_rhs = 3 < n_rhs = 4
     gram = (4, d, d, d, None, 8, d, d, d) + tail
@@ -65,7 +67,7 @@ def test_messages_name_the_entry_that_was_called():
 
 def test_argument_checks_need_no_device():
     from grf_amd import _lib
-    lib = _lib.load()
+    lib = abi_contract.device_less_lib()  # (made-up pointers: never in a process that sees a GPU)
     d = ctypes.c_void_p(8)  # (never dereferenced: every call below is refused by its argument checks)
     big = 1 << 40
 

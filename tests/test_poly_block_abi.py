@@ -5,6 +5,8 @@ import ctypes
 import os
 import re
 
+import abi_contract
+
 NEW = ["grf_poly_kernel_block_workspace_bytes", "grf_poly_kernel_block_f64", "grf_poly_kernel_diag_workspace_bytes",
        "grf_poly_kernel_diag_f64", "grf_poly_kernel_grad_workspace_bytes", "grf_poly_kernel_grad_f64"]
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "grf.h")
@@ -50,7 +52,7 @@ def test_workspace_sizes():
 
 def test_argument_checks_need_no_device():
     from grf_amd import _lib
-    lib = _lib.load()
+    lib = abi_contract.device_less_lib()  # (made-up pointers: never in a process that sees a GPU)
     d = ctypes.c_void_p(8)  # (never dereferenced: every call below is refused or returns before any device work)
     EINVAL, EUNSUP, OK = _lib.GRF_EINVAL, _lib.GRF_EUNSUPPORTED, 0
 

@@ -6,6 +6,8 @@ import ctypes
 import os
 import re
 
+import abi_contract
+
 NEW = ["grf_posterior_rhs_f64", "grf_posterior_reduce_workspace_bytes", "grf_posterior_reduce_f64"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "grf.h")
@@ -59,7 +61,7 @@ def test_workspace_size_is_positive_and_monotone():
 
 def test_argument_checks_need_no_device():
     from grf_amd import _lib
-    lib = _lib.load()
+    lib = abi_contract.device_less_lib()  # (made-up pointers: never in a process that sees a GPU)
     EINVAL, EUNSUP = _lib.GRF_EINVAL, _lib.GRF_EUNSUPPORTED
     P = lambda k: ctypes.c_void_p(k << 24)  # noqa: E731  (never dereferenced: every call below is refused or empty)
     b, x, al, pr, va, me, ws = (P(k) for k in range(1, 8))

@@ -5,6 +5,8 @@ import ctypes
 import os
 import re
 
+import abi_contract
+
 NEW = ["grf_spgemm_workspace_bytes", "grf_spgemm_csr_count", "grf_spgemm_csr_fill"]
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "grf.h")
 
@@ -43,7 +45,7 @@ def test_constants_agree_between_header_and_binding():
 
 def test_argument_checks_need_no_device():
     from grf_amd import _lib
-    lib = _lib.load()
+    lib = abi_contract.device_less_lib()  # (made-up pointers: never in a process that sees a GPU)
     d = ctypes.c_void_p(8)  # (never dereferenced: every call below is refused by its argument checks)
     need = lib.grf_spgemm_workspace_bytes(5, 7, 1000)
     # counters + the row queue + at least one wave's bitmap (n_cols bits) and ranks (an int32 per 64 columns)
