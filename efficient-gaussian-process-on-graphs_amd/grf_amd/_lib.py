@@ -1,4 +1,4 @@
-"""ctypes binding of ``libgrf_amd.so`` (the C ABI declared in ``include/grf.h``).
+"""ctypes binding of ``libgrf_amd.so`` (the C ABI declared in ``include/grf.h`` and ``include/grf_dense_solve.h``).
 
 The shared library is built in-tree by ``csrc/Makefile`` (hipcc, gfx950).  If
 it is missing this module raises -- there is no CPU fallback anywhere in the
@@ -207,7 +207,15 @@ SIGNATURES = {
     "grf_pcg_poly_solve_lanczos_f64": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _dbl,
                                               _vp, _i64, _i32, _dbl, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp, _i64,
                                               _vp, _vp]),
+    # include/grf_dense_solve.h: the fp64 Cholesky factorisation and triangular solves of the dense exact GPR
+    "grf_potrf_f64_workspace_bytes": (_sz, [_i64]),
+    "grf_potrf_f64": (_i32, [_i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "grf_trsm_f64_workspace_bytes": (_sz, [_i64, _i64]),
+    "grf_trsm_f64": (_i32, [_i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _sz, _vp]),
 }
+# the entries declared in include/grf_dense_solve.h (additive: include/grf.h and its ABI revision are unchanged)
+DENSE_SOLVE = ("grf_potrf_f64_workspace_bytes", "grf_potrf_f64", "grf_trsm_f64_workspace_bytes", "grf_trsm_f64")
+DENSE_SOLVE_NB = 128  # include/grf_dense_solve.h GRF_DENSE_SOLVE_NB
 
 _lib = None
 
@@ -262,4 +270,10 @@ def check(rc: int, what: str) -> None:
 
 
 def exported_symbols() -> list[str]:
-    return sorted(SIGNATURES)
+    """The functions include/grf.h declares."""
+    return sorted(set(SIGNATURES) - set(DENSE_SOLVE))
+
+
+def exported_symbols_dense_solve() -> list[str]:
+    """The functions include/grf_dense_solve.h declares."""
+    return sorted(DENSE_SOLVE)

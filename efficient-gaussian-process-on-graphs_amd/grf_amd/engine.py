@@ -1585,6 +1585,60 @@ class GRFEngine:
                                           ws.numel(), self.stream), "grf_expm_sym_f64")
         return E
 
+    # ------------------------------------- dense exact GPR: the fp64 Cholesky factorisation and triangular solves
+    def _cached_ws(self, name: str, need: int) -> torch.Tensor:
+        """The call family's workspace, kept between calls and grown on demand (calls on this engine's stream are
+        ordered, and every call rewrites what it reads)."""
+        cache = self.__dict__.setdefault("_dense_solve_ws", {})
+        ws = cache.get(name)
+        if ws is None or ws.numel() < need:
+            ws = cache[name] = self._ws(need)
+        return ws
+
+    def cholesky(self, A: torch.Tensor):
+        """(F, logdet, info) of grf_potrf_f64 for a symmetric positive-definite ``A`` (n x n; only its lower triangle
+        and diagonal are read): F (n x n fp64) holds L below and L^T mirrored above, ``logdet`` (one fp64) is
+        2 sum log L_ii, ``info`` (one int32) is 0 or the 1-based index of the first pivot that is not positive and
+        finite (then logdet is NaN).  All three stay on the device: no host read."""
+        A = self._dense_f64(A, "cholesky: A")
+        n = int(A.shape[0])
+        if A.shape[1] != n or n < 1:
+            raise ValueError("cholesky: A must be square and non-empty")
+        need = int(self.lib.grf_potrf_f64_workspace_bytes(n))
+        ws = self._cached_ws("potrf", need)
+        self._dense_memory_guard("cholesky", n, n * n * 8)
+        F = torch.empty((n, n), dtype=torch.float64, device=self.device)
+        logdet = torch.empty(1, dtype=torch.float64, device=self.device)
+        info = torch.empty(1, dtype=torch.int32, device=self.device)
+        C.check(self.lib.grf_potrf_f64(n, _p(A), self._pitch(A), _p(F), n, _p(logdet), _p(info), _p(ws), ws.numel(),
+                                       self.stream), "grf_potrf_f64")
+        return F, logdet, info
+
+    def cholesky_solve(self, F: torch.Tensor, B: torch.Tensor, transposed: Optional[bool] = None,
+                       inplace: bool = False) -> torch.Tensor:
+        """Triangular solves with the factor of ``cholesky`` (grf_trsm_f64).  ``B`` is nrhs x n, ONE RIGHT-HAND SIDE
+        PER ROW.  ``transposed=False``: L x = b; ``True``: L^T x = b; ``None`` (default): both, x = (L L^T)^-1 b.
+        Returns the solutions in B's layout (a new tensor unless ``inplace`` and B is already an fp64 matrix on the
+        device with contiguous rows)."""
+        F = self._dense_f64(F, "cholesky_solve: F")
+        n = int(F.shape[0])
+        if F.shape[1] != n:
+            raise ValueError("cholesky_solve: F must be square")
+        Bd = self._dense_f64(B, "cholesky_solve: B")
+        if Bd.shape[1] != n:
+            raise ValueError(f"cholesky_solve: B must be (nrhs x {n}), one right-hand side per row")
+        if Bd is B and not inplace:
+            Bd = B.clone(memory_format=torch.contiguous_format)
+        nrhs = int(Bd.shape[0])
+        if n == 0 or nrhs == 0:
+            return Bd
+        need = int(self.lib.grf_trsm_f64_workspace_bytes(n, nrhs))
+        ws = self._cached_ws("trsm", need)
+        for t in ((0, 1) if transposed is None else (int(bool(transposed)),)):
+            C.check(self.lib.grf_trsm_f64(n, nrhs, _p(F), self._pitch(F), t, _p(Bd), self._pitch(Bd), _p(ws),
+                                          ws.numel(), self.stream), "grf_trsm_f64")
+        return Bd
+
     def laplacian_dense_matrix(self, W, mode: int) -> torch.Tensor:
         """The Laplacian of grf_laplacian_dense as a dense fp64 n x n device matrix."""
         G = self.walk_matrix_dense(W, mode)

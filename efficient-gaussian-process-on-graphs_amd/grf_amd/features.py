@@ -492,3 +492,79 @@ class DenseGramFunction(torch.autograd.Function):
         (f,) = ctx.saved_tensors
         grad = ctx.steps.grad(f, g)
         return grad.to(device=f.device, dtype=f.dtype), None
+
+
+# ------------------------------------------------------------------ the dense exact GPR (gpflow.models.GPR)
+_LOG_2PI = float(np.log(2.0 * np.pi))
+
+
+def gpr_factor(K: torch.Tensor, noise: torch.Tensor, engine: Optional[GRFEngine] = None):
+    """(F, logdet, info) of ``GRFEngine.cholesky`` for K^ = K + noise I (K widened to fp64; no host read)."""
+    eng = engine or get_engine()
+    Kh = K.detach().to(eng.device, torch.float64, copy=True)
+    Kh.diagonal().add_(noise.detach().to(eng.device, torch.float64).reshape(()))
+    return eng.cholesky(Kh)
+
+
+class GPRLogMarginalLikelihoodFunction(torch.autograd.Function):
+    """log N(Y | 0, K + noise I) summed over Y's p columns (gpflow.models.GPR.log_marginal_likelihood), on the
+    fp64 Cholesky of grf_potrf_f64 and the solves of grf_trsm_f64, with K^ = K + noise I and alpha = K^^-1 Y:
+
+        lml = -1/2 sum_c y_c^T alpha_c - (p / 2) logdet K^ - (n p / 2) log 2 pi
+        dL/dK = 1/2 (alpha alpha^T - p K^^-1),   dL/dnoise = trace(dL/dK),   dL/dY = -alpha.
+
+    K^^-1 is two grf_trsm_f64 passes on the identity, alpha alpha^T - p K^^-1 one grf_gemm_nt_f64 call with Z.
+    No host synchronisation in either direction.  Returns (lml, info): with info != 0 (K^ not positive definite)
+    the value is NaN."""
+
+    @staticmethod
+    def forward(ctx, K: torch.Tensor, noise: torch.Tensor, Y: torch.Tensor, eng: GRFEngine, factor):
+        n, p = int(Y.shape[0]), int(Y.shape[1])
+        F, logdet, info = factor if factor is not None else gpr_factor(K, noise, eng)
+        Yt = Y.detach().to(eng.device, torch.float64).t().contiguous()           # p x n: one right-hand side per row
+        alpha_t = eng.cholesky_solve(F, Yt)                                       # (K^^-1 Y)^T
+        quad = (Yt * alpha_t).sum()
+        lml = -0.5 * quad - 0.5 * p * logdet[0] - 0.5 * n * p * _LOG_2PI
+        ctx.eng, ctx.F, ctx.alpha_t = eng, F, alpha_t
+        ctx.meta = (K.dtype, K.device, noise.dtype, noise.device, noise.shape, Y.dtype, Y.device)
+        ctx.mark_non_differentiable(info)
+        return lml, info
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor, _g_info):
+        eng, F, alpha_t = ctx.eng, ctx.F, ctx.alpha_t
+        k_dtype, k_dev, n_dtype, n_dev, n_shape, y_dtype, y_dev = ctx.meta
+        p, n = int(alpha_t.shape[0]), int(alpha_t.shape[1])
+        g = g.to(eng.device, torch.float64)
+        gK = gn = gY = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            Kinv = eng.cholesky_solve(F, torch.eye(n, dtype=torch.float64, device=eng.device), inplace=True)
+            alpha = alpha_t.t().contiguous()                                      # n x p
+            G = eng.gemm_nt_f64(alpha, alpha, alpha=0.5, gamma=-0.5 * p, Z=Kinv, out=Kinv, symmetric=True)
+            if ctx.needs_input_grad[1]:
+                gn = (g * G.diagonal().sum()).reshape(n_shape).to(device=n_dev, dtype=n_dtype)
+            if ctx.needs_input_grad[0]:
+                gK = (g * G).to(device=k_dev, dtype=k_dtype)
+        if ctx.needs_input_grad[2]:
+            gY = (-g * alpha_t.t()).to(device=y_dev, dtype=y_dtype)
+        return gK, gn, gY, None, None
+
+
+def gpr_log_marginal_likelihood(K: torch.Tensor, noise, Y: torch.Tensor, factor=None,
+                                engine: Optional[GRFEngine] = None):
+    """(lml, info) of the dense exact GP regression: K (n x n, fp32 as ``K_torch`` returns it or fp64; widened to
+    fp64), noise (a one-element tensor; a float is a constant), Y (n x p), zero mean, summed over the p columns as
+    GPflow does.  ``lml`` is a differentiable fp64 scalar on the engine's device (gradients to K, noise and Y);
+    ``info`` is the device int32 of the factorisation (non-zero: K + noise I is not positive definite and lml is
+    NaN).  ``factor``: a (F, logdet, info) of ``gpr_factor`` for the same K and noise, to share one factorisation
+    with other uses."""
+    if K.dim() != 2 or K.shape[0] != K.shape[1] or K.shape[0] < 1:
+        raise ValueError("gpr_log_marginal_likelihood: K must be square and non-empty")
+    if Y.dim() != 2 or Y.shape[0] != K.shape[0] or Y.shape[1] < 1:
+        raise ValueError(f"gpr_log_marginal_likelihood: Y must be ({K.shape[0]} x p)")
+    eng = engine or get_engine()
+    if not torch.is_tensor(noise):
+        noise = torch.tensor(float(noise), dtype=torch.float64, device=eng.device)
+    if noise.numel() != 1:
+        raise ValueError("gpr_log_marginal_likelihood: noise must have one element")
+    return GPRLogMarginalLikelihoodFunction.apply(K, noise, Y, eng, factor)
