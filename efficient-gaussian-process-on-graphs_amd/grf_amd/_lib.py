@@ -1,4 +1,5 @@
-"""ctypes binding of ``libgrf_amd.so`` (the C ABI declared in ``include/grf.h`` and ``include/grf_dense_solve.h``).
+"""ctypes binding of ``libgrf_amd.so`` (the C ABI declared in ``include/grf.h``, ``include/grf_dense_solve.h`` and
+``include/grf_svgp.h``).
 
 The shared library is built in-tree by ``csrc/Makefile`` (hipcc, gfx950).  If
 it is missing this module raises -- there is no CPU fallback anywhere in the
@@ -217,6 +218,17 @@ SIGNATURES = {
 DENSE_SOLVE = ("grf_potrf_f64_workspace_bytes", "grf_potrf_f64", "grf_trsm_f64_workspace_bytes", "grf_trsm_f64")
 DENSE_SOLVE_NB = 128  # include/grf_dense_solve.h GRF_DENSE_SOLVE_NB
 
+
+# include/grf_svgp.h (additive as well): the RobustMax likelihood's quadrature, its predictive probabilities and the
+# conditional variance's row sums of squares.  A mapping of its own: SIGNATURES keeps naming what it named
+SVGP_SIGNATURES = {
+    "grf_robustmax_ve_f64": (_i32, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _dbl, _vp, _vp, _i64, _vp,
+                                    _i64, _vp]),
+    "grf_robustmax_predict_f64": (_i32, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _dbl, _vp, _i64, _vp]),
+    "grf_rows_sqsum_f64": (_i32, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
+}
+SVGP_MAX_CLASSES, SVGP_MAX_GH = 64, 64  # include/grf_svgp.h GRF_SVGP_MAX_CLASSES, GRF_SVGP_MAX_GH
+
 _lib = None
 
 
@@ -245,7 +257,7 @@ def load():
     if got != ABI_VERSION:
         raise ImportError(f"grf_amd: {LIB_PATH} implements ABI revision {got}, this binding needs {ABI_VERSION} "
                           f"(rebuild it with `make -C {CSRC}`)")
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SVGP_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -277,3 +289,8 @@ def exported_symbols() -> list[str]:
 def exported_symbols_dense_solve() -> list[str]:
     """The functions include/grf_dense_solve.h declares."""
     return sorted(DENSE_SOLVE)
+
+
+def exported_symbols_svgp() -> list[str]:
+    """The functions include/grf_svgp.h declares."""
+    return sorted(SVGP_SIGNATURES)

@@ -1639,6 +1639,67 @@ class GRFEngine:
                                           ws.numel(), self.stream), "grf_trsm_f64")
         return Bd
 
+    # ------------------------------------- SVGP classification (include/grf_svgp.h): the RobustMax quadrature
+    GH_POINTS = 20  # gpflow.likelihoods.MultiClass's num_gauss_hermite_points
+
+    def _gauss_hermite(self):
+        """numpy's hermgauss(20) nodes and weights on the device (what GPflow calls), uploaded once per engine."""
+        gh = self.__dict__.get("_gh")
+        if gh is None:
+            x, w = np.polynomial.hermite.hermgauss(self.GH_POINTS)
+            gh = self.__dict__["_gh"] = (torch.from_numpy(x).to(self.device), torch.from_numpy(w).to(self.device))
+        return gh
+
+    def _latents(self, mu: torch.Tensor, var: torch.Tensor, what: str):
+        mu, var = self._dense_f64(mu, f"{what}: mu"), self._dense_f64(var, f"{what}: var")
+        if mu.shape != var.shape:
+            raise ValueError(f"{what}: mu and var must have one shape (n x P)")
+        return mu, var, int(mu.shape[0]), int(mu.shape[1])
+
+    def robustmax_ve(self, mu: torch.Tensor, var: torch.Tensor, y: torch.Tensor, with_grad: bool = True,
+                     epsilon: float = 1e-3):
+        """MultiClass(RobustMax)'s variational expectations (grf_robustmax_ve_f64): ``mu`` and ``var`` n x P fp64,
+        ``y`` n int32 labels on the device.  Returns (ve (n,), d ve/d mu, d ve/d var) -- the gradients (n x P) are
+        None without ``with_grad``.  A label outside [0, P) gives a NaN row.  No host read."""
+        mu, var, n, P = self._latents(mu, var, "robustmax_ve")
+        if y.dtype != torch.int32 or y.device != self.device or y.dim() != 1 or y.numel() != n or not y.is_contiguous():
+            raise ValueError("robustmax_ve: y must be a contiguous int32 vector of n labels on this device")
+        gx, gw = self._gauss_hermite()
+        ve = torch.empty(n, dtype=torch.float64, device=self.device)
+        dmu = torch.empty((n, P), dtype=torch.float64, device=self.device) if with_grad else None
+        dvar = torch.empty((n, P), dtype=torch.float64, device=self.device) if with_grad else None
+        C.check(self.lib.grf_robustmax_ve_f64(n, P, _p(mu), self._pitch(mu), _p(var), self._pitch(var), _p(y), _p(gx),
+                                              _p(gw), gx.numel(), float(epsilon), _p(ve), _p(dmu), P, _p(dvar), P,
+                                              self.stream), "grf_robustmax_ve_f64")
+        return ve, dmu, dvar
+
+    def robustmax_predict(self, mu: torch.Tensor, var: torch.Tensor, epsilon: float = 1e-3) -> torch.Tensor:
+        """The predictive class probabilities ps (n x P) of MultiClass._predict_mean_and_var
+        (grf_robustmax_predict_f64)."""
+        mu, var, n, P = self._latents(mu, var, "robustmax_predict")
+        gx, gw = self._gauss_hermite()
+        ps = torch.empty((n, P), dtype=torch.float64, device=self.device)
+        C.check(self.lib.grf_robustmax_predict_f64(n, P, _p(mu), self._pitch(mu), _p(var), self._pitch(var), _p(gx),
+                                                   _p(gw), gx.numel(), float(epsilon), _p(ps), P, self.stream),
+                "grf_robustmax_predict_f64")
+        return ps
+
+    def rows_sqsum(self, T: torch.Tensor, groups: int, base: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out[r, g] = base[r] + sum_j T[r, g len + j]^2 for the ``groups`` equal column groups of T (n x groups len)
+        in a fixed order (grf_rows_sqsum_f64); ``base``: n fp64 values or None."""
+        T = self._dense_f64(T, "rows_sqsum: T")
+        n, width, groups = int(T.shape[0]), int(T.shape[1]), int(groups)
+        if groups < 1 or width % groups:
+            raise ValueError(f"rows_sqsum: T's {width} columns do not split into {groups} equal groups")
+        if base is not None:
+            base = base.to(self.device, torch.float64).contiguous()
+            if base.dim() != 1 or base.numel() != n:
+                raise ValueError("rows_sqsum: base must hold one value per row of T")
+        out = torch.empty((n, groups), dtype=torch.float64, device=self.device)
+        C.check(self.lib.grf_rows_sqsum_f64(n, groups, width // groups, _p(T), self._pitch(T), _p(base), _p(out),
+                                            groups, self.stream), "grf_rows_sqsum_f64")
+        return out
+
     def laplacian_dense_matrix(self, W, mode: int) -> torch.Tensor:
         """The Laplacian of grf_laplacian_dense as a dense fp64 n x n device matrix."""
         G = self.walk_matrix_dense(W, mode)

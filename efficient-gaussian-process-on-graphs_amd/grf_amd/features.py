@@ -568,3 +568,130 @@ def gpr_log_marginal_likelihood(K: torch.Tensor, noise, Y: torch.Tensor, factor=
     if noise.numel() != 1:
         raise ValueError("gpr_log_marginal_likelihood: noise must have one element")
     return GPRLogMarginalLikelihoodFunction.apply(K, noise, Y, eng, factor)
+
+
+# ------------------------------------------------------------------ the sparse variational GP (gpflow.models.SVGP)
+def svgp_factor(Kmm: torch.Tensor, jitter: float, engine: Optional[GRFEngine] = None):
+    """(F, logdet, info) of ``GRFEngine.cholesky`` for Kmm + jitter I (Kmm widened to fp64; no host read)."""
+    eng = engine or get_engine()
+    Kh = Kmm.detach().to(eng.device, torch.float64, copy=True)
+    Kh.diagonal().add_(float(jitter))
+    return eng.cholesky(Kh)
+
+
+def svgp_conditional(eng: GRFEngine, F: torch.Tensor, Knm: torch.Tensor, Knn_diag: torch.Tensor, q_mu: torch.Tensor,
+                     Lq: torch.Tensor):
+    """GPflow's whitened base_conditional with a full q_sqrt: (AT, T, fmean, fvar) for the factor F of Kmm.
+    AT (N x M): row n is Lm^-1 k_n (one forward solve, the data points as right-hand-side rows; ``Knm`` is solved
+    in place and must be the caller's own copy); fmean = AT q_mu (N x P); T = AT [Lq_1 ... Lq_P] (N x P M: one
+    product against the stacked transposes); fvar[n, p] = Knn[n] - sum_m AT[n, m]^2 + sum_j T_p[n, j]^2."""
+    P, M = int(Lq.shape[0]), int(Lq.shape[1])
+    AT = eng.cholesky_solve(F, Knm, transposed=False, inplace=True)
+    fmean = eng.gemm_nt_f64(AT, q_mu.t().contiguous())
+    T = eng.gemm_nt_f64(AT, Lq.transpose(1, 2).reshape(P * M, M))
+    base = Knn_diag - eng.rows_sqsum(AT, 1)[:, 0]
+    fvar = eng.rows_sqsum(T, P, base)
+    return AT, T, fmean, fvar
+
+
+class SVGPElboFunction(torch.autograd.Function):
+    """The whitened SVGP evidence lower bound, elbo = scale sum_n ve_n - KL (gpflow.models.SVGP.elbo with
+    whiten=True, full q_sqrt), on grf_potrf_f64, grf_trsm_f64, grf_gemm_nt_f64, grf_rows_sqsum_f64 and the
+    likelihood's expectations (grf_robustmax_ve_f64 for MultiClass):
+
+        Lm = chol(Kmm + jitter I),  AT = (Lm^-1 Kmn)^T,  fmean = AT q_mu,  T_p = AT Lq_p,  Lq_p = tril(q_sqrt_p),
+        fvar[n, p] = Knn[n] - sum_m AT[n, m]^2 + sum_j T_p[n, j]^2,
+        KL = 1/2 (sum q_mu^2 - P M - sum_p sum_m log Lq_p[m, m]^2 + sum Lq^2).
+
+    Backward, with Gm = d/dfmean, Gv = d/dfvar (N x P, from the likelihood's own launch), W_p = 2 Gv_p o T_p:
+        d/dq_mu = AT^T Gm - q_mu,    d/dLq_p = tril(AT^T W_p - Lq_p + diag(1 / Lq_p[m, m])),    d/dKnn = sum_p Gv_p,
+        ATbar   = Gm q_mu^T + sum_p W_p Lq_p^T - 2 (sum_p Gv_p) o AT,
+        Knm_bar = ATbar Lm^-1 (rows Lm^-T abar_n),    L_bar = -tril(Kmn_bar A),
+        Kmm_bar = sym(Lm^-T Phi(Lm^T L_bar) Lm^-1),   Phi: the lower triangle with the diagonal halved,
+    by grf_gemm_nt_f64, cholesky_solve, transposes and tril only.  No host synchronisation in either direction.
+    Returns (elbo, info): with info != 0 (Kmm + jitter I not positive definite) the value is NaN."""
+
+    @staticmethod
+    def forward(ctx, Kmm, Knm, Knn_diag, q_mu, q_sqrt, lik_param, Y, likelihood, scale, jitter, eng, factor):
+        dev, f64 = eng.device, torch.float64
+        F, _logdet, info = factor if factor is not None else svgp_factor(Kmm, jitter, eng)
+        qm = q_mu.detach().to(dev, f64)
+        Lq = torch.tril(q_sqrt.detach().to(dev, f64))
+        P, M = int(Lq.shape[0]), int(Lq.shape[1])
+        Knn = Knn_diag.detach().to(dev, f64)
+        AT, T, fmean, fvar = svgp_conditional(eng, F, Knm.detach().to(dev, f64, copy=True), Knn, qm, Lq)
+        par = lik_param.detach().to(dev, f64) if lik_param is not None else None
+        ve, gmu, gvar, gpar = likelihood.variational_expectations(eng, fmean, fvar, Y, par, with_grad=True)
+        kl = 0.5 * ((qm * qm).sum() - float(P * M) - torch.log(Lq.diagonal(dim1=1, dim2=2) ** 2).sum()
+                    + (Lq * Lq).sum())
+        elbo = float(scale) * ve.sum() - kl
+        elbo = torch.where(info[0] != 0, torch.full_like(elbo, float("nan")), elbo)
+        ctx.eng, ctx.scale = eng, float(scale)
+        ctx.saved = (F, AT, T, qm, Lq, gmu, gvar, gpar)
+        ctx.meta = [(t.dtype, t.device) if t is not None else None for t in (Kmm, Knm, Knn_diag, q_mu, q_sqrt,
+                                                                             lik_param)]
+        ctx.mark_non_differentiable(info)
+        return elbo, info
+
+    @staticmethod
+    def backward(ctx, g, _g_info):
+        eng = ctx.eng
+        F, AT, T, qm, Lq, gmu, gvar, gpar = ctx.saved
+        N, M, P = int(AT.shape[0]), int(AT.shape[1]), int(Lq.shape[0])
+        g = g.to(eng.device, torch.float64)
+        gs = g * ctx.scale
+        Gm, Gv = gs * gmu, gs * gvar
+        A = AT.t().contiguous()                                                      # M x N
+        g_qmu = eng.gemm_nt_f64(A, Gm.t().contiguous()) - g * qm                     # AT^T Gm - q_mu
+        W = ((2.0 * Gv)[:, :, None] * T.view(N, P, M)).reshape(N, P * M)
+        g_LqT = eng.gemm_nt_f64(W.t().contiguous(), A)                               # rows (p, j): (AT^T W_p)[:, j]
+        diag = Lq.diagonal(dim1=1, dim2=2)
+        g_qsqrt = torch.tril(g_LqT.view(P, M, M).transpose(1, 2) - g * (Lq - torch.diag_embed(1.0 / diag)))
+        Gs = Gv.sum(dim=1)
+        ATbar = eng.gemm_nt_f64(Gm, qm)                                              # Gm q_mu^T
+        ATbar = eng.gemm_nt_f64(W, Lq.permute(1, 0, 2).reshape(M, P * M), gamma=1.0, Z=ATbar, out=ATbar)
+        ATbar.sub_((2.0 * Gs)[:, None] * AT)
+        del W
+        g_Kmm = g_Knm = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            Knm_bar = eng.cholesky_solve(F, ATbar, transposed=True, inplace=True)    # N x M: rows Lm^-T abar_n
+            g_Knm = Knm_bar
+            if ctx.needs_input_grad[0]:
+                L_bar = -torch.tril(eng.gemm_nt_f64(Knm_bar.t().contiguous(), A))
+                S = eng.gemm_nt_f64(torch.triu(F), L_bar.t().contiguous())          # Lm^T L_bar
+                Phi = torch.tril(S)
+                Phi.diagonal().mul_(0.5)
+                X = eng.cholesky_solve(F, Phi, transposed=True, inplace=True)        # Phi Lm^-1
+                X = eng.cholesky_solve(F, X.t().contiguous(), transposed=True, inplace=True)
+                g_Kmm = 0.5 * (X + X.t())
+        grads = [g_Kmm, g_Knm, Gs, g_qmu, g_qsqrt, gs * gpar if gpar is not None else None]
+        out = []
+        for need, meta, t in zip(ctx.needs_input_grad[:6], ctx.meta, grads):
+            out.append(t.to(device=meta[1], dtype=meta[0]) if need and t is not None else None)
+        return (*out, None, None, None, None, None, None)
+
+
+def svgp_elbo(Kmm: torch.Tensor, Knm: torch.Tensor, Knn_diag: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor,
+              Y: torch.Tensor, likelihood, scale: float = 1.0, jitter: float = 1e-6, factor=None,
+              engine: Optional[GRFEngine] = None):
+    """(elbo, info) of the whitened sparse variational GP: Kmm (M x M), Knm (N x M), Knn_diag (N), fp32 as ``K_torch``
+    returns them or fp64 (widened); q_mu (M x P), q_sqrt (P x M x M, its lower triangles are read); Y as the
+    likelihood wants it (``efficient_graph_gp.likelihoods``: int32 labels on the device for MultiClass, N x P
+    values for Gaussian).  ``elbo`` is a differentiable fp64 scalar on the engine's device (gradients to Kmm, Knm,
+    Knn_diag, q_mu, q_sqrt's lower triangle and a Gaussian likelihood's variance); ``info`` is the device int32 of
+    the factorisation (non-zero: Kmm + jitter I is not positive definite and elbo is NaN).  ``factor``: a
+    (F, logdet, info) of ``svgp_factor`` for the same Kmm and jitter."""
+    if Kmm.dim() != 2 or Kmm.shape[0] != Kmm.shape[1] or Kmm.shape[0] < 1:
+        raise ValueError("svgp_elbo: Kmm must be square and non-empty")
+    M = int(Kmm.shape[0])
+    if Knm.dim() != 2 or Knm.shape[1] != M or Knm.shape[0] < 1:
+        raise ValueError(f"svgp_elbo: Knm must be (N x {M})")
+    N = int(Knm.shape[0])
+    if Knn_diag.dim() != 1 or Knn_diag.numel() != N:
+        raise ValueError(f"svgp_elbo: Knn_diag must hold {N} values")
+    if q_mu.dim() != 2 or q_mu.shape[0] != M or q_sqrt.dim() != 3 or \
+            tuple(q_sqrt.shape) != (q_mu.shape[1], M, M):
+        raise ValueError(f"svgp_elbo: q_mu must be ({M} x P) and q_sqrt (P x {M} x {M})")
+    eng = engine or get_engine()
+    par = likelihood.parameter()
+    return SVGPElboFunction.apply(Kmm, Knm, Knn_diag, q_mu, q_sqrt, par, Y, likelihood, scale, jitter, eng, factor)
